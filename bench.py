@@ -9,7 +9,10 @@ weights (no network), closed-loop at fixed concurrency so the continuous
 batcher runs saturated; a "step" is one engine iteration (one varlen
 prefill batch or one decode batch over all running sequences).
 
-Usage:  python bench.py --gpus N --steps K --warmup W
+Usage:  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run does only what the headline figure needs: engine setup, warmup,
+K timed steps, the optional output dump, one JSON result line. Measurements
+beyond the headline belong behind --full.
 For N>1 the driver launches this via torch.distributed.run with one rank
 per GPU; ranks are independent replicas (weak scaling) synchronized only
 at the timing barriers.
@@ -55,7 +58,55 @@ def parse_args():
     ap.add_argument("--cp", type=int, default=1,
                     help="prefill-context-parallel degree (rows chunked "
                          "across ranks, replicated decode); world = tp*cp")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the engine "
+                         "returned to its caller as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline "
+                         "figure (a plain run has none to skip yet)")
     return ap.parse_args()
+
+
+_DUMP_BYTES_MAX = 64 * 2**20
+
+
+def _req_index(request_id: str) -> int:
+    # engine-assigned ids are "req-<n>", n = submission order
+    return int(request_id.rsplit("-", 1)[-1])
+
+
+def dump_outputs(out_dir: str, step_outs: list) -> None:
+    """Write the StepOutputs the timed steps returned, as float64 arrays.
+
+    last_step_*: one entry per output of the final timed step, in the order
+    step() returned them. timed_steps: [steps, max outputs per step, 3] of
+    (request index, token id, finished) for every timed step, rows padded
+    with -1 — the async decode pipeline may hand a step's tokens back one
+    call later, so a single step can legitimately return nothing. When the
+    full history would exceed the size cap only the latest steps are kept.
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def rows(outs):
+        return np.array([[_req_index(o.request_id), o.token_id,
+                          1.0 if o.finished else 0.0] for o in outs],
+                        dtype=np.float64).reshape(-1, 3)
+
+    last = rows(step_outs[-1]) if step_outs else np.zeros((0, 3))
+    np.save(os.path.join(out_dir, "last_step_request_index.npy"), last[:, 0])
+    np.save(os.path.join(out_dir, "last_step_token_ids.npy"), last[:, 1])
+    np.save(os.path.join(out_dir, "last_step_finished.npy"), last[:, 2])
+
+    width = max([len(o) for o in step_outs] + [1])
+    budget = _DUMP_BYTES_MAX - 3 * last.nbytes - 4096
+    keep = max(1, min(len(step_outs), budget // (width * 3 * 8)))
+    hist = np.full((keep, width, 3), -1.0, dtype=np.float64)
+    for i, outs in enumerate(step_outs[len(step_outs) - keep:]):
+        if outs:
+            hist[i, :len(outs)] = rows(outs)
+    np.save(os.path.join(out_dir, "timed_steps.npy"), hist)
 
 
 def main():
@@ -214,11 +265,13 @@ def main():
     ttft_track[0] = True
     t0 = time.perf_counter()
     tokens = 0
+    step_outs = []
     for _ in range(args.steps):
         refill()
         outs = eng.step()
         tokens += len(outs)
         record_first_tokens(outs)
+        step_outs.append(outs)
     barrier_sync()
     elapsed = time.perf_counter() - t0
 
@@ -236,6 +289,11 @@ def main():
             tot_tokens = int(tt.item())
     else:
         tot_tokens = tokens
+
+    if args.dump_outputs:
+        out_dir = (args.dump_outputs if world == 1
+                   else os.path.join(args.dump_outputs, f"rank{rank}"))
+        dump_outputs(out_dir, step_outs)
 
     ttfts.sort()
     p50_ttft_ms = (ttfts[len(ttfts) // 2] * 1000) if ttfts else None

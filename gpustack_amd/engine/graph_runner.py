@@ -13,6 +13,7 @@ scratch, never in live KV.
 """
 from __future__ import annotations
 
+import gc
 import os
 
 import torch
@@ -89,20 +90,32 @@ class DecodeGraphRunner:
 
     def capture(self) -> None:
         model, kv = self.runner.model, self.runner.kv
-        pool = torch.cuda.graph_pool_handle()
-        for bs in reversed(self.buckets):  # largest first reserves the pool
-            meta = self._meta(bs)
-            model(self.tokens[:bs], meta, kv,
-                  return_both=self.want_hidden)  # eager warmup (blas workspaces)
+        # a dead engine is cyclic garbage (runner <-> graph runner); if the
+        # cycle collector fires inside a capture it destroys that engine's
+        # graphs, pool blocks and pinned buffers mid-capture, which the HIP
+        # runtime rejects and the process aborts. Collect now, and keep the
+        # collector off until every bucket is captured.
+        gc.collect()
+        gc_was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            pool = torch.cuda.graph_pool_handle()
+            for bs in reversed(self.buckets):  # largest first reserves the pool
+                meta = self._meta(bs)
+                model(self.tokens[:bs], meta, kv,
+                      return_both=self.want_hidden)  # eager warmup (blas workspaces)
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, pool=pool):
+                    out = model(self.tokens[:bs], meta, kv,
+                                return_both=self.want_hidden)
+                self.graphs[bs] = g
+                self.outs[bs] = out
+                self.metas[bs] = meta  # keep every referenced tensor alive
             torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool):
-                out = model(self.tokens[:bs], meta, kv,
-                            return_both=self.want_hidden)
-            self.graphs[bs] = g
-            self.outs[bs] = out
-            self.metas[bs] = meta  # keep every referenced tensor alive
-        torch.cuda.synchronize()
+        finally:
+            if gc_was_enabled:
+                gc.enable()
 
     def can_run(self, batch: ScheduledBatch) -> bool:
         return ((not batch.is_prefill)

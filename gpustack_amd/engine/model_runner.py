@@ -238,10 +238,12 @@ class ModelRunner:
             # MLA (DeepSeek): latent attention serves on the CPU oracle
             # path today; the CDNA4 absorbed-attention kernels are the r3
             # item — refuse loudly rather than crash mid-capture
-            if torch.device(cfg.device).type == "cuda":
+            if torch.device(cfg.device).type == "cuda" \
+                    and os.environ.get("GPUSTACK_AMD_MLA_KERNEL") != "1":
                 raise NotImplementedError(
-                    "MLA (DeepSeek) GPU serving requires the r3 CDNA4 "
-                    "absorbed-attention kernels; CPU serving is available")
+                    "MLA (DeepSeek) GPU serving requires the gated CDNA4 "
+                    "absorbed-attention kernels (set "
+                    "GPUSTACK_AMD_MLA_KERNEL=1); CPU serving is available")
             if cfg.kv_cache_dtype == "fp8":
                 raise ValueError("fp8 KV is not supported with MLA latent "
                                  "caches yet")
@@ -396,12 +398,15 @@ class ModelRunner:
             # OPT-IN for now: the targeted eagle/spec GPU tests pass with
             # them, but the full suite showed a crash in sequence with
             # other engines on one box — isolate before defaulting on.
+            # MLA decode stays eager: its latent-cache write reads a mask
+            # back to the host, which a capture cannot contain.
             eagle_graphs = (self.eagle is not None
                             and os.environ.get("GPUSTACK_AMD_EAGLE_GRAPHS",
                                                "0") == "1")
             if graphs_enabled() and moe_graph_ok \
                     and (self.eagle is None or eagle_graphs) \
                     and self.comm.pp_size == 1 \
+                    and not cfg.spec.kv_lora_rank \
                     and self.model.offload is None:
                 self.graph_runner = DecodeGraphRunner(
                     self, want_hidden=self.eagle is not None)

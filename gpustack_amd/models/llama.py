@@ -1125,8 +1125,10 @@ class LlamaForCausalLM(nn.Module):
             if self.spec.embed_scale:
                 # Gemma: sqrt(hidden) embedding scale, cast like HF
                 # (normalizer materialized in the embed dtype)
+                # (rounded on the host: building a device scalar here is a
+                # host-to-device copy, which hipGraph capture forbids)
                 x = x * torch.tensor(self.spec.embed_scale,
-                                     dtype=x.dtype, device=x.device)
+                                     dtype=x.dtype).item()
         residual = None
         off = self.offload
         if off is not None:

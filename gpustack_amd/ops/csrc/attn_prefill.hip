@@ -115,6 +115,13 @@ __global__ __launch_bounds__(PF_THREADS) void flash_prefill_kernel(
 #pragma unroll
   for (int r = 0; r < KU; ++r) kst_kv[r] = (tid + r * PF_THREADS) / (D / 8);
   const int kst_d0 = (tid % (D / 8)) * 8;
+  // a thread keeps one d0 for every round only while PF_THREADS is a
+  // multiple of the row's unit count; D=192 (24 units per row) is not
+  constexpr bool D0_FIXED = PF_THREADS % (D / 8) == 0;
+  auto kst_d0_at = [&](int r) {
+    if constexpr (D0_FIXED) return kst_d0;
+    else return ((tid + r * PF_THREADS) % (D / 8)) * 8;
+  };
   const int vst_d = tid % DVK;
   const int vst_kvc0 = (tid / DVK) * 8;  // + r*(8*PF_THREADS/DVK) per round
   constexpr int VST_STEP = 8 * PF_THREADS / DVK;
@@ -128,7 +135,7 @@ __global__ __launch_bounds__(PF_THREADS) void flash_prefill_kernel(
       const int kv = kv0 + kst_kv[r];
       kstage[r] = (kv < len)
           ? *reinterpret_cast<const u16x8*>(
-                k + (long)(seq0 + kv) * ks + (long)kvh * D + kst_d0)
+                k + (long)(seq0 + kv) * ks + (long)kvh * D + kst_d0_at(r))
           : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
 #pragma unroll
@@ -148,7 +155,7 @@ __global__ __launch_bounds__(PF_THREADS) void flash_prefill_kernel(
 #pragma unroll
     for (int r = 0; r < KU; ++r) {
       *reinterpret_cast<u16x8*>(reinterpret_cast<char*>(Kl) +
-                                kswz<D>(kst_kv[r], kst_d0 * 2)) = kstage[r];
+                                kswz<D>(kst_kv[r], kst_d0_at(r) * 2)) = kstage[r];
     }
 #pragma unroll
     for (int r = 0; r < VU; ++r) {

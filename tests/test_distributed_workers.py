@@ -130,6 +130,15 @@ def test_orphan_cleanup_kills_stale_engine_process(tmp_path):
         "--kv-cache-blocks", "32", "--max-model-len", "128",
     ], start_new_session=True)
     try:
+        # a stale engine has been up for a while; right after spawn the
+        # kernel may still show an empty /proc/<pid>/cmdline, which the
+        # identity check (rightly) refuses to kill on
+        for _ in range(100):
+            with open(f"/proc/{proc.pid}/cmdline", "rb") as f:
+                if b"gpustack_amd.worker.engine_server" in f.read().split(b"\0"):
+                    break
+            _t.sleep(0.05)
+
         class _FakeClient:
             def list_instances(self, worker_id=None):
                 return [{"id": 1, "pid": proc.pid, "model_name": "tiny-orphan",

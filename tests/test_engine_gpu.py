@@ -247,16 +247,22 @@ def test_guided_json_gpu():
     assert isinstance(doc["ok"], bool)
 
 
-# ---- gated engine-level serving for the r3 kernel variants ----------------
+# ---- engine-level serving on the opt-in kernel variants (the tests set the
+# opt-in themselves) ---------------------------------------------------------
 
-import os as _os
 
-_oss_engine = pytest.mark.skipif(
-    _os.environ.get("GPUSTACK_AMD_OSS_KERNELS") != "1",
-    reason="set GPUSTACK_AMD_OSS_KERNELS=1 after the r3 kernel validation")
-_mla_engine = pytest.mark.skipif(
-    _os.environ.get("GPUSTACK_AMD_MLA_KERNEL") != "1",
-    reason="set GPUSTACK_AMD_MLA_KERNEL=1 after the r3 kernel validation")
+@pytest.fixture
+def _oss_kernels(monkeypatch):
+    monkeypatch.setenv("GPUSTACK_AMD_OSS_KERNELS", "1")
+
+
+@pytest.fixture
+def _mla_kernel(monkeypatch):
+    monkeypatch.setenv("GPUSTACK_AMD_MLA_KERNEL", "1")
+
+
+_oss_engine = pytest.mark.usefixtures("_oss_kernels")
+_mla_engine = pytest.mark.usefixtures("_mla_kernel")
 
 
 @_oss_engine
