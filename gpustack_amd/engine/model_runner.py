@@ -224,7 +224,7 @@ class ModelRunner:
                 or cfg.spec.norm_type != "rmsnorm"
                 or cfg.spec.head_dim not in (128,)) \
                 and not cfg.spec.kv_lora_rank \
-                and os.environ.get("GPUSTACK_AMD_OSS_KERNELS") != "1":
+                and not ops.oss_kernels_enabled():
             # GPT-OSS / Gemma-class specs need the gated kernel variants;
             # refuse at init with a clear message instead of crashing
             # inside hipGraph capture on the first forward
@@ -239,7 +239,7 @@ class ModelRunner:
             # path today; the CDNA4 absorbed-attention kernels are the r3
             # item — refuse loudly rather than crash mid-capture
             if torch.device(cfg.device).type == "cuda" \
-                    and os.environ.get("GPUSTACK_AMD_MLA_KERNEL") != "1":
+                    and not ops.mla_kernel_enabled():
                 raise NotImplementedError(
                     "MLA (DeepSeek) GPU serving requires the gated CDNA4 "
                     "absorbed-attention kernels (set "

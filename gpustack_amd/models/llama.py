@@ -336,8 +336,6 @@ class MLAAttention(nn.Module):
         return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], -1)
 
     def forward(self, x, meta: ForwardMeta, cos_sin, k_cache, v_cache):
-        import os as _os
-
         T = x.shape[0]
         # mixed prefill batches (decode rows riding along) keep the loud
         # default: the per-seq tables in meta cover prefill seqs only
@@ -345,7 +343,7 @@ class MLAAttention(nn.Module):
                 or (meta.block_tables is not None
                     and (meta.num_prefill_tokens or T) == T))
         gpu_ok = (x.is_cuda
-                  and _os.environ.get("GPUSTACK_AMD_MLA_KERNEL") == "1"
+                  and ops.mla_kernel_enabled()
                   and self.r == 512 and self.dr == 64 and self.nh % 16 == 0
                   and pure)
         if x.is_cuda and not gpu_ok:
@@ -806,7 +804,7 @@ class MoEMLP(nn.Module):
         # numerics pass (same gate as the attention sinks/window kernels)
         act_ok = (self.spec.moe_act == "silu" and self.gate_up_b is None) or (
             self.spec.moe_act == "clamped_swiglu"
-            and os.environ.get("GPUSTACK_AMD_OSS_KERNELS") == "1")
+            and ops.oss_kernels_enabled())
         return (x.is_cuda and x.dtype == torch.bfloat16
                 and os.environ.get("GPUSTACK_AMD_FUSED_MOE", "1") == "1"
                 and act_ok

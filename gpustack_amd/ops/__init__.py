@@ -57,7 +57,7 @@ def _backend(t: torch.Tensor):
     return None
 
 
-def _oss_kernels_enabled() -> bool:
+def oss_kernels_enabled() -> bool:
     """GPT-OSS CDNA4 kernel variants (head_dim-64 + attention sinks +
     sliding window in attn_decode/attn_prefill.hip) are written and
     compile-checked but not yet GPU-validated — opt in explicitly until
@@ -65,8 +65,27 @@ def _oss_kernels_enabled() -> bool:
     return os.environ.get("GPUSTACK_AMD_OSS_KERNELS", "0") == "1"
 
 
-def _mla_kernel_enabled() -> bool:
+def mla_kernel_enabled() -> bool:
     return os.environ.get("GPUSTACK_AMD_MLA_KERNEL", "0") == "1"
+
+
+def _require_validated_variant(kind: str, q, sinks, window, softcap,
+                               mla_shape: bool = False) -> None:
+    """The sinks/window/softcap and D!=128 attention kernel variants are
+    written but not yet GPU-validated — fail loudly rather than silently
+    mis-attend (opt in with GPUSTACK_AMD_OSS_KERNELS=1; r3 flips the
+    default after the validation pass). `mla_shape`: the op also serves the
+    192/128 MLA expand shape, under the MLA opt-in."""
+    D = q.shape[-1]
+    d_ok = D == 128 or (mla_shape and D == 192 and mla_kernel_enabled())
+    if (sinks is not None or window or softcap or not d_ok) \
+            and not oss_kernels_enabled():
+        mla_hint = ("(or GPUSTACK_AMD_MLA_KERNEL=1 for the 192/128 MLA "
+                    "expand shape) " if mla_shape else "")
+        raise NotImplementedError(
+            f"sinks/window/softcap/D!=128 CDNA4 {kind} kernel variants "
+            f"are unvalidated — set GPUSTACK_AMD_OSS_KERNELS=1 {mla_hint}"
+            "to opt in")
 
 
 def _sinks_f32(sinks):
@@ -135,11 +154,7 @@ def greedy_sample_into(out, logits) -> None:
 
 def greedy_sample(logits) -> torch.Tensor:
     out = torch.empty(logits.shape[0], dtype=torch.long, device=logits.device)
-    hip = _backend(logits)
-    if hip is not None:
-        hip.greedy_sample(out, logits)
-    else:
-        torch_ref.greedy_sample(out, logits)
+    greedy_sample_into(out, logits)
     return out
 
 
@@ -148,15 +163,7 @@ def paged_attn_decode(out, q, k_cache, v_cache, block_tables, seq_lens,
                       softcap: float = 0.0) -> None:
     hip = _backend(q)
     if hip is not None:
-        if (sinks is not None or window or softcap or q.shape[-1] != 128) \
-                and not _oss_kernels_enabled():
-            # the sinks/window/softcap and D!=128 kernel variants are
-            # written but not yet GPU-validated — fail loudly rather than
-            # silently mis-attend (opt in with GPUSTACK_AMD_OSS_KERNELS=1;
-            # r3 flips the default after the validation pass)
-            raise NotImplementedError(
-                "sinks/window/softcap/D!=128 CDNA4 decode kernel variants "
-                "are unvalidated — set GPUSTACK_AMD_OSS_KERNELS=1 to opt in")
+        _require_validated_variant("decode", q, sinks, window, softcap)
         hip.paged_attn_decode(out, q, k_cache, v_cache, block_tables, seq_lens,
                               scale, sinks=_sinks_f32(sinks), window=window,
                               softcap=softcap)
@@ -200,15 +207,8 @@ def varlen_prefill_attn(out, q, k, v, seq_lens: list[int], scale: float,
                         softcap: float = 0.0) -> None:
     hip = _backend(q)
     if hip is not None:
-        d_ok = (q.shape[-1] == 128
-                or (q.shape[-1] == 192 and _mla_kernel_enabled()))
-        if (sinks is not None or window or softcap or not d_ok) \
-                and not _oss_kernels_enabled():
-            raise NotImplementedError(
-                "sinks/window/softcap/D!=128 CDNA4 prefill kernel variants "
-                "are unvalidated — set GPUSTACK_AMD_OSS_KERNELS=1 (or "
-                "GPUSTACK_AMD_MLA_KERNEL=1 for the 192/128 MLA expand "
-                "shape) to opt in")
+        _require_validated_variant("prefill", q, sinks, window, softcap,
+                                   mla_shape=True)
         if tiles is None or tiles[0] is None:
             tiles = build_prefill_tiles(seq_lens, q.device)
         hip.flash_prefill(out, q, k, v, tiles[0], tiles[1], tiles[2], scale,
@@ -246,12 +246,8 @@ def paged_prefill_attn(out, q, k_cache, v_cache, block_tables,
     (removes the r1-measured ~3.5x paged-decode-row penalty)."""
     hip = _backend(q)
     if hip is not None:
-        if (sinks is not None or window or softcap or q.shape[-1] != 128) \
-                and not _oss_kernels_enabled():
-            raise NotImplementedError(
-                "sinks/window/softcap/D!=128 CDNA4 paged-prefill kernel "
-                "variants are unvalidated — set GPUSTACK_AMD_OSS_KERNELS=1 "
-                "to opt in")
+        _require_validated_variant("paged-prefill", q, sinks, window,
+                                   softcap)
         if tiles is None:
             tiles = build_paged_prefill_tiles(seq_starts, seq_hists,
                                               seq_news, q.device)

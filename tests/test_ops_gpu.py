@@ -350,7 +350,8 @@ def test_flash_prefill_paged(Hq, Hkv, cases):
 
 def test_flash_prefill_paged_matches_contiguous():
     """hist=0 paged prefill == the contiguous varlen prefill kernel on the
-    same data (cross-kernel consistency)."""
+    same data, bit for bit: both kernels run one device body, so only the
+    K/V source differs and the arithmetic order is the same."""
     D, BS, Hq, Hkv = 128, 16, 32, 8
     lens = [64, 129, 7]
     T = sum(lens)
@@ -383,7 +384,8 @@ def test_flash_prefill_paged_matches_contiguous():
     out_p = torch.empty_like(q)
     ops.paged_prefill_attn(out_p, q, k_cache, v_cache, bt, starts,
                            [0] * len(lens), lens, 1.0 / math.sqrt(D))
-    _close(out_p, out_c)
+    assert torch.equal(out_p, out_c), \
+        f"max abs diff {(out_p.float() - out_c.float()).abs().max().item()}"
 
 
 @pytest.mark.parametrize("T,E,topk,H,I", [
@@ -621,6 +623,73 @@ def test_oss_paged_prefill(D, cases, sink, window):
     R.paged_prefill_attn(ref, q, kc, vc, bt, starts, hists, news, scale,
                          sinks=sinks, window=window)
     _close(out, ref)
+
+
+def _ext_cross_case():
+    """D=64 EXT inputs (sinks + window 8 + softcap 30) for the contiguous
+    vs paged cross-check: a one-row sequence, a partial tile, and 150
+    tokens = three q tiles x three kv tiles, the window narrower than a
+    pool block and (at q0=128) dropping the first kv tile whole. K/V are
+    also scattered into a pool through a shuffled block table. Inputs come
+    from a private CPU generator so they do not depend on test order."""
+    D, Hq, Hkv, BS = 64, 8, 2, 16
+    lens = [1, 17, 150]
+    T = sum(lens)
+    g = torch.Generator().manual_seed(4321)
+    mk = lambda *shape: (torch.randn(*shape, generator=g) / 4).to(
+        device="cuda", dtype=torch.bfloat16)
+    q, k, v = mk(T, Hq, D), mk(T, Hkv, D), mk(T, Hkv, D)
+    sinks = torch.randn(Hq, generator=g).cuda()
+    nb_per = [(L + BS - 1) // BS for L in lens]
+    nblocks = sum(nb_per) + 1
+    perm = (torch.randperm(nblocks - 1, generator=g) + 1).to(torch.int32)
+    bt = torch.zeros(len(lens), max(nb_per), dtype=torch.int32, device="cuda")
+    blk_of, off_of, used = [], [], 0
+    for i, L in enumerate(lens):
+        row = perm[used:used + nb_per[i]]
+        bt[i, :nb_per[i]] = row.cuda()
+        blk_of += [int(row[p // BS]) for p in range(L)]
+        off_of += [p % BS for p in range(L)]
+        used += nb_per[i]
+    kc = torch.zeros(nblocks, Hkv, BS, D, dtype=torch.bfloat16, device="cuda")
+    vc = torch.zeros_like(kc)
+    kc[blk_of, :, off_of] = k
+    vc[blk_of, :, off_of] = v
+    kw = dict(sinks=sinks, window=8, softcap=30.0)
+    return lens, q, k, v, kc, vc, bt, 1 / math.sqrt(D), kw
+
+
+@oss
+def test_oss_prefill_paged_matches_contiguous_ext():
+    """EXT path (sinks/window/softcap, D=64): both prefill kernels vs
+    torch_ref, and hist=0 paged == contiguous bit for bit (one body)."""
+    lens, q, k, v, kc, vc, bt, scale, kw = _ext_cross_case()
+    starts = [sum(lens[:i]) for i in range(len(lens))]
+    out_c, out_p, ref = (torch.empty_like(q) for _ in range(3))
+    ops.varlen_prefill_attn(out_c, q, k, v, lens, scale, **kw)
+    ops.paged_prefill_attn(out_p, q, kc, vc, bt, starts, [0] * len(lens),
+                           lens, scale, **kw)
+    R.varlen_prefill_attn(ref, q, k, v, lens, scale, **kw)
+    _close(out_c, ref)
+    _close(out_p, ref)
+    assert torch.equal(out_p, out_c), \
+        f"max abs diff {(out_p.float() - out_c.float()).abs().max().item()}"
+
+
+@oss
+def test_oss_prefill_paged_history_matches_contiguous_ext():
+    """The 150-token sequence served as hist=100 + 50 new rows gives rows
+    100..149 of the contiguous EXT output (window counted from the
+    absolute position, across pool-block and kv-tile boundaries)."""
+    lens, q, k, v, kc, vc, bt, scale, kw = _ext_cross_case()
+    out_c = torch.empty_like(q)
+    ops.varlen_prefill_attn(out_c, q, k, v, lens, scale, **kw)
+    s2 = sum(lens[:2])
+    qn = q[s2 + 100:s2 + 150].contiguous()
+    out_p = torch.empty_like(qn)
+    ops.paged_prefill_attn(out_p, qn, kc, vc, bt[2:3].contiguous(), [0],
+                           [100], [50], scale, **kw)
+    _close(out_p, out_c[s2 + 100:s2 + 150])
 
 
 @oss
