@@ -245,7 +245,7 @@ class LLMEngine:
             and not batch.is_prefill
             and not batch.is_suffix
             and batch.rows_per_seq == 1
-            and all(s.params.greedy and not s.params.logprobs
+            and all(not s.params.logprobs
                     and not s.params.top_logprobs
                     and not s.params.needs_logit_processing
                     for s in batch.seqs)

@@ -16,6 +16,38 @@ from .scheduler import ScheduledBatch
 from .sequence import Sequence
 
 
+def sample_row_params(seqs: list[Sequence]):
+    """Per-row arguments of ops.sample_into for `seqs`, as Python lists:
+    (temperature, top_k, top_p, min_p, seed, step). `step` counts the tokens
+    the sequence has sampled so far, read back or still in flight, so
+    synchronous and async stepping consume the same random stream; the r-th
+    occurrence of one Sequence in `seqs` uses step + r."""
+    temps, ks, ps, mps, seeds, steps = [], [], [], [], [], []
+    seen: dict[int, int] = {}
+    for s in seqs:
+        r = seen.get(id(s), 0)
+        seen[id(s)] = r + 1
+        p = s.params
+        temps.append(float(p.temperature))
+        ks.append(min(max(int(p.top_k), 0), 2**31 - 1))
+        ps.append(float(p.top_p))
+        mps.append(float(p.min_p))
+        seed = s.sample_seed & (2**64 - 1)  # u64 bits in an int64 slot
+        seeds.append(seed - 2**64 if seed >= 2**63 else seed)
+        steps.append(len(s.output_token_ids) + s.pending_tokens + r)
+    return temps, ks, ps, mps, seeds, steps
+
+
+def _sample_param_views(buf: torch.Tensor, mb: int, bs: int):
+    """(temperature, top_k, top_p, min_p, seed, step) views of one packed
+    staging buffer (4*mb int64 words), cut to the first bs rows."""
+    f1 = buf[2 * mb:3 * mb].view(torch.float32)
+    w3 = buf[3 * mb:4 * mb]
+    return (f1[:mb][:bs], w3.view(torch.int32)[mb:][:bs], f1[mb:][:bs],
+            w3.view(torch.float32)[:mb][:bs], buf[:mb][:bs],
+            buf[mb:2 * mb][:bs])
+
+
 class Sampler:
     def __init__(self, device, model_eos_token_id: int | None = None):
         self.device = device
@@ -177,6 +209,23 @@ class Sampler:
         for i in proc_greedy:
             row = self._process_logits(logits[i].float(), seqs[i])
             out[i] = int(row.argmax())
+        plain_idx = [i for i in rand_idx
+                     if not seqs[i].params.needs_logit_processing]
+        if plain_idx:
+            # plain random rows: one fused on-device draw for all of them
+            params = sample_row_params(seqs)
+            dev = logits.device
+            cols = [torch.tensor([col[i] for i in plain_idx], dtype=dt,
+                                 device=dev)
+                    for col, dt in zip(params, (torch.float32, torch.int32,
+                                                torch.float32, torch.float32,
+                                                torch.long, torch.long))]
+            ids = torch.empty(len(plain_idx), dtype=torch.long, device=dev)
+            ops.sample_into(ids, logits[plain_idx], *cols)
+            for i, tok in zip(plain_idx, ids.tolist()):
+                out[i] = tok
+            rand_idx = [i for i in rand_idx
+                        if seqs[i].params.needs_logit_processing]
         if rand_idx:
             lg = logits[rand_idx].float()
             temps = torch.tensor(
@@ -299,6 +348,14 @@ class ModelRunner:
         self._sampled_pin = [torch.zeros(mb, dtype=torch.long, pin_memory=pin)
                              for _ in range(2)]
         self._pin_idx = 0
+        self._async_sampled = False  # last async step had a sampled row
+        # per-row sampling parameters of async steps with sampled rows:
+        # packed into one buffer so a step uploads them in a single copy
+        self._sample_args_dev = torch.zeros(4 * mb, dtype=torch.long,
+                                            device=self.device)
+        self._sample_args_pin = [torch.zeros(4 * mb, dtype=torch.long,
+                                             pin_memory=pin)
+                                 for _ in range(2)]
 
     def _init_tunableop(self) -> None:
         """hipBLASLt algorithm selection via torch TunableOp.
@@ -760,12 +817,13 @@ class ModelRunner:
 
     @torch.inference_mode()
     def execute_async(self, batch: ScheduledBatch, reuse_tokens: bool):
-        """Submit a greedy decode step without reading results back.
+        """Submit a decode step without reading results back.
 
         Samples on-device into the persistent buffer and starts an async
         D2H copy; read_sampled() collects it one step later. With
-        reuse_tokens, the previous step's sampled ids feed this step's
-        token input device-side (no host round-trip at all)."""
+        reuse_tokens, the batch holds the sequences of the previous async
+        step in the same order, and that step's sampled ids feed this
+        step's token input device-side (no host round-trip at all)."""
         bs = len(batch.seqs)
         token_src = self._sampled_dev if reuse_tokens else None
         if (self.graph_runner is not None and self.graph_runner.can_run(batch)
@@ -776,11 +834,25 @@ class ModelRunner:
             if token_src is not None:
                 tokens = token_src[:bs].to(self.device)
             logits = self.model(tokens, meta, self.kv)
-        from .. import ops
-
-        ops.greedy_sample_into(self._sampled_dev[:bs], logits)
         slot = self._pin_idx
         self._pin_idx ^= 1
+        if not reuse_tokens:
+            # reuse_tokens: the rows of the previous async step again, so
+            # the answer stands (one pass over a large batch costs more
+            # host time than the sampling kernel takes)
+            self._async_sampled = not all(s.params.greedy for s in batch.seqs)
+        if not self._async_sampled:
+            ops.greedy_sample_into(self._sampled_dev[:bs], logits)
+        else:
+            mb = self.cfg.max_num_seqs
+            stage = self._sample_args_pin[slot]
+            for view, col in zip(_sample_param_views(stage, mb, bs),
+                                 sample_row_params(batch.seqs)):
+                view.copy_(torch.tensor(col, dtype=view.dtype))
+            self._sample_args_dev.copy_(stage, non_blocking=True)
+            ops.sample_into(self._sampled_dev[:bs], logits,
+                            *_sample_param_views(self._sample_args_dev, mb,
+                                                 bs))
         self._sampled_pin[slot][:bs].copy_(self._sampled_dev[:bs], non_blocking=True)
         if self.device.type == "cuda":
             ev = torch.cuda.Event()

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import enum
+import random
 import time
 from dataclasses import dataclass, field
 
@@ -90,6 +91,15 @@ class Sequence:
     finish_time: float | None = None
     finish_reason: str | None = None
     preemptions: int = 0
+    # key of this sequence's random stream (ops.sample_into): the request's
+    # seed when it gave one, else drawn once here
+    sample_seed: int | None = None
+
+    def __post_init__(self) -> None:
+        if self.sample_seed is None:
+            seed = self.params.seed
+            self.sample_seed = (int(seed) if seed is not None
+                                else random.getrandbits(63))
 
     @property
     def num_tokens(self) -> int:

@@ -158,6 +158,19 @@ def greedy_sample(logits) -> torch.Tensor:
     return out
 
 
+def sample_into(out, logits, temperature, top_k, top_p, min_p, seed,
+                step) -> None:
+    """Draw one token per logits row from that row's own parameters
+    (f32 temperature/top_p/min_p, i32 top_k, i64 seed/step, all [N]);
+    rows with temperature <= 0 get the argmax."""
+    hip = _backend(logits)
+    if hip is not None:
+        hip.sample(out, logits, temperature, top_k, top_p, min_p, seed, step)
+    else:
+        torch_ref.sample(out, logits, temperature, top_k, top_p, min_p, seed,
+                         step)
+
+
 def paged_attn_decode(out, q, k_cache, v_cache, block_tables, seq_lens,
                       scale: float, sinks=None, window: int = 0,
                       softcap: float = 0.0) -> None:

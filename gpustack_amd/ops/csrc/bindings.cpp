@@ -11,6 +11,7 @@ void rope_neox_launch(const long*, void*, void*, const float*, int, int, int, in
 void silu_and_mul_launch(void*, const void*, long, int, hipStream_t);
 void reshape_and_cache_launch(const void*, const void*, void*, void*, const long*, int, int, int, int, long, long, int, hipStream_t);
 void greedy_sample_launch(long*, const void*, int, int, hipStream_t);
+void sample_launch(long*, const void*, const float*, const int*, const float*, const float*, const long*, const long*, int, int, hipStream_t);
 void mla_decode_launch(float*, const void*, const void*, const int*, const int*, int, int, int, int, int, int, float, int*, hipStream_t);
 void paged_attn_decode_launch(void*, const void*, const void*, const void*, const int*, const int*, int, int, int, int, int, float, long, int, const float*, int, float, int*, hipStream_t);
 void flash_prefill_launch(void*, const void*, const void*, const void*, const int*, const int*, const int*, int, int, int, int, int, float, long, long, long, const float*, int, float, int*, hipStream_t);
@@ -136,6 +137,36 @@ void greedy_sample(at::Tensor out, at::Tensor logits) {
   const int N = logits.size(0), V = logits.size(1);
   greedy_sample_launch(out.data_ptr<long>(), logits.data_ptr(), N, V,
                        cur_stream(logits));
+  HIP_CHECK_LAST();
+}
+
+void check_row_param(const at::Tensor& t, at::ScalarType dtype, long n,
+                     const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == dtype, name, " has the wrong dtype");
+  TORCH_CHECK(t.dim() == 1 && t.size(0) == n && t.is_contiguous(),
+              name, " must be contiguous [N]");
+}
+
+void sample(at::Tensor out, at::Tensor logits, at::Tensor temperature,
+            at::Tensor top_k, at::Tensor top_p, at::Tensor min_p,
+            at::Tensor seed, at::Tensor step) {
+  check_bf16(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2, "logits must be [N, V]");
+  const long N = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= (1L << 30), "vocab size out of range");
+  check_row_param(out, at::kLong, N, "out");
+  check_row_param(temperature, at::kFloat, N, "temperature");
+  check_row_param(top_k, at::kInt, N, "top_k");
+  check_row_param(top_p, at::kFloat, N, "top_p");
+  check_row_param(min_p, at::kFloat, N, "min_p");
+  check_row_param(seed, at::kLong, N, "seed");
+  check_row_param(step, at::kLong, N, "step");
+  sample_launch(out.data_ptr<long>(), logits.data_ptr(),
+                temperature.data_ptr<float>(), top_k.data_ptr<int>(),
+                top_p.data_ptr<float>(), min_p.data_ptr<float>(),
+                seed.data_ptr<long>(), step.data_ptr<long>(), (int)N, (int)V,
+                cur_stream(logits));
   HIP_CHECK_LAST();
 }
 
@@ -405,6 +436,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("silu_and_mul", &silu_and_mul, "silu(x[:d])*x[d:]");
   m.def("reshape_and_cache", &reshape_and_cache, "scatter K/V into paged pool");
   m.def("greedy_sample", &greedy_sample, "argmax over vocab");
+  m.def("sample", &sample, "per-row top-k/top-p/min-p sampling");
   m.def("mla_decode", &mla_decode,
         "MLA absorbed decode over the paged latent cache (DeepSeek)");
   m.def("paged_attn_decode", &paged_attn_decode, "paged GQA decode attention",

@@ -186,6 +186,101 @@ def greedy_sample(out: torch.Tensor, logits: torch.Tensor) -> None:
     out.copy_(logits.float().argmax(dim=-1))
 
 
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = 0xFFFFFFFF
+
+
+def philox4x32(counter, key) -> list[int]:
+    """Philox4x32-10: four 32-bit counter words, two key words -> four
+    32-bit output words (Python ints)."""
+    c = [int(x) & _U32 for x in counter]
+    k = [int(x) & _U32 for x in key]
+    for _ in range(10):
+        p0 = _PHILOX_M0 * c[0]
+        p1 = _PHILOX_M1 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k[0], p1 & _U32,
+             (p0 >> 32) ^ c[3] ^ k[1], p0 & _U32]
+        k = [(k[0] + _PHILOX_W0) & _U32, (k[1] + _PHILOX_W1) & _U32]
+    return c
+
+
+def philox_uniform(seed: int, step: int) -> float:
+    """The sampler's uniform in [0, 1): the top 24 bits of the first
+    Philox word under key = seed, counter = (step, 0, 0), both as u64."""
+    seed, step = int(seed), int(step)
+    x0 = philox4x32([step, step >> 32, 0, 0], [seed, seed >> 32])[0]
+    return (x0 >> 8) * 2.0 ** -24
+
+
+def _sample_kept(lf: torch.Tensor, temperature: torch.Tensor,
+                 top_k: torch.Tensor, top_p: torch.Tensor,
+                 min_p: torch.Tensor):
+    """(kept mask, fp32 weights) of fp32 rows lf [N, V] with temperature > 0.
+    Each filter is a value threshold on the full row, so every token equal
+    to a boundary value is kept; the kept set is their intersection."""
+    N, V = lf.shape
+    w = torch.exp((lf - lf.max(dim=1, keepdim=True).values)
+                  / temperature.unsqueeze(1))
+    w = torch.nan_to_num(w, nan=0.0).clamp_(0.0, 1.0)
+    kept = (min_p <= 0).unsqueeze(1) | (w >= min_p.unsqueeze(1))
+    sv, si = torch.sort(lf, dim=1, descending=True)
+    k_on = (top_k > 0) & (top_k < V)
+    kth = sv.gather(1, (top_k.long() - 1).clamp(0, V - 1).unsqueeze(1))
+    kept &= ~k_on.unsqueeze(1) | (lf >= kth)
+    # mass of the tokens strictly greater than each value: the running sum
+    # in descending order, taken at the first token of each run of equals
+    sw = w.gather(1, si).double()
+    before = sw.cumsum(1) - sw
+    first = torch.ones_like(sv, dtype=torch.bool)
+    first[:, 1:] = sv[:, 1:] != sv[:, :-1]
+    greater = torch.cummax(torch.where(first, before, 0.0), dim=1).values
+    Z = sw.sum(dim=1, keepdim=True)
+    ok = torch.zeros_like(first).scatter_(
+        1, si, greater <= top_p.double().unsqueeze(1) * Z)
+    kept &= (top_p >= 1).unsqueeze(1) | ok
+    return kept, w
+
+
+def sample_kept(row: torch.Tensor, temperature: float, top_k: int,
+                top_p: float, min_p: float):
+    """(kept mask, fp32 weights) of one logits row for temperature > 0."""
+    kept, w = _sample_kept(
+        row.float().unsqueeze(0), torch.tensor([float(temperature)]),
+        torch.tensor([int(top_k)]), torch.tensor([float(top_p)]),
+        torch.tensor([float(min_p)]))
+    return kept[0], w[0]
+
+
+def sample(out: torch.Tensor, logits: torch.Tensor, temperature, top_k,
+           top_p, min_p, seed, step) -> None:
+    """Per-row top-k/top-p/min-p draw, the definition sample.hip follows:
+    temperature <= 0 -> argmax (lowest index on ties); else the inverse CDF
+    of the kept weights in token-index order at u = philox_uniform."""
+    lf = logits.float().cpu()
+    N, V = lf.shape
+    T = torch.as_tensor(temperature, dtype=torch.float32).cpu()
+    amax = lf.argmax(dim=1)  # first maximal value
+    rand = T > 0
+    kept, w = _sample_kept(
+        lf, torch.where(rand, T, torch.ones_like(T)),
+        torch.as_tensor(top_k).cpu(), torch.as_tensor(top_p).float().cpu(),
+        torch.as_tensor(min_p).float().cpu())
+    wk = torch.where(kept, w, torch.zeros_like(w)).double()
+    cum = wk.cumsum(1)
+    S = cum[:, -1]
+    u = torch.tensor([philox_uniform(s, t) for s, t in
+                      zip(torch.as_tensor(seed).tolist(),
+                          torch.as_tensor(step).tolist())],
+                     dtype=torch.float64)
+    hit = cum > (u * S).unsqueeze(1)
+    tok = hit.int().argmax(dim=1)  # first running sum above u*S
+    # rounding left none above it: the last kept token with weight
+    last = V - 1 - (wk > 0).flip(1).int().argmax(dim=1)
+    tok = torch.where(hit.any(dim=1), tok, last)
+    out.copy_(torch.where(rand & (S > 0), tok, amax))
+
+
 def _sink_softmax(att: torch.Tensor, sinks: torch.Tensor | None):
     """softmax over the kv axis with optional per-head SINK logits joining
     the denominator only (GPT-OSS: probability mass the sinks absorb is
