@@ -631,6 +631,11 @@ class EngineConfig:
     # int4 in HBM after load and decode GEMMs dequantize in-register
     # (ops/csrc/w4_gemm.hip) — 70B-class models stay resident packed
     # instead of inflating to bf16 (reference: vLLM --quantization)
+    # FP8 runtime ("fp8"): dynamic W8A8 — the dense attention/MLP
+    # projections are held as OCP e4m3fn with one f32 scale per output
+    # channel, activations are quantized per token at each use
+    # (ops/csrc/fp8_gemm.hip). lm_head, embeddings, MLA projections and
+    # MoE expert banks stay bf16; not combinable with cpu_offload_gb yet
     quantize_runtime: str | None = None
     # CPU weight offload (reference: vLLM --cpu-offload-gb, the GGUF
     # partial-offload placement): ~this many GiB of trailing layers'

@@ -331,6 +331,18 @@ class ModelRunner:
 
             logging.getLogger(__name__).info(
                 "W4 runtime: %d weight tensors packed int4", n)
+        if getattr(cfg, "quantize_runtime", None) == "fp8":
+            if getattr(cfg, "cpu_offload_gb", 0) > 0:
+                raise ValueError(
+                    "quantize_runtime='fp8' with cpu_offload_gb > 0 is not "
+                    "supported yet")
+            from ..models.weights import convert_to_fp8_runtime
+
+            n = convert_to_fp8_runtime(self.model, cfg)
+            import logging
+
+            logging.getLogger(__name__).info(
+                "FP8 runtime: %d weight tensors packed e4m3 (W8A8)", n)
         if getattr(cfg, "cpu_offload_gb", 0) > 0:
             from .offload import setup_cpu_offload
 

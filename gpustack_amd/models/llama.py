@@ -68,8 +68,25 @@ class W4Pack:
         self.shape = (qw.shape[0], qw.shape[1] * 2)
 
 
-def qlinear(x, w, pack: "W4Pack | None", bias=None):
-    """F.linear with an optional W4 runtime pack.
+class Fp8Pack:
+    """Runtime FP8 weight (weights.convert_to_fp8_runtime): qw
+    float8_e4m3fn [N, K] (OCP, not fnuz), ws f32 [N] per-output-channel
+    scale. Activations are quantized per token at each use (dynamic W8A8,
+    ops.fp8_linear)."""
+
+    __slots__ = ("qw", "ws", "shape")
+
+    def __init__(self, qw, ws):
+        self.qw, self.ws = qw, ws
+        self.shape = tuple(qw.shape)
+
+
+def qlinear(x, w, pack: "W4Pack | Fp8Pack | None", bias=None):
+    """F.linear with an optional runtime pack (W4Pack or Fp8Pack).
+
+    Fp8Pack: ops.fp8_linear (bias added after).
+
+    W4Pack:
 
     Default GPU path: the w4_dequant HIP kernel expands the packed weight
     into a transient bf16 tensor (allocator-cached) and hipBLASLt runs the
@@ -80,6 +97,8 @@ def qlinear(x, w, pack: "W4Pack | None", bias=None):
     dequant+hipBLASLt at serving shapes so far (profiles/r04)."""
     if pack is None:
         return F.linear(x, w, bias)
+    if isinstance(pack, Fp8Pack):
+        return ops.fp8_linear(x, pack.qw, pack.ws, bias)
     if x.is_cuda:
         import os as _os
 

@@ -734,3 +734,49 @@ def convert_to_w4_runtime(model, cfg: EngineConfig) -> int:
     if model.device.type == "cuda":
         torch.cuda.empty_cache()
     return n_packed
+
+
+def convert_to_fp8_runtime(model, cfg: EngineConfig) -> int:
+    """Quantize the dense serving projections to FP8 (OCP e4m3fn, one f32
+    scale per output channel; ops/torch_ref.py has the definition) and free
+    their bf16 parameters. Activations are quantized per token at each use
+    (dynamic W8A8, ops/csrc/fp8_gemm.hip). Returns the number of packed
+    tensors.
+
+    Runs after load and LoRA merge, per rank, on the already-sharded
+    weights. Packed: attn.qkv_w, attn.o_w, dense mlp.gate_up_w / down_w
+    (including the dense-first layers of MoE models). Shapes with N%128 or
+    K%128 keep bf16 — mixed execution is fine.
+
+    Stays bf16:
+      - lm_head and the embeddings (the sampler reads these logits);
+      - MLA attention projections (no qlinear dispatch there);
+      - MoE expert banks (the fused MoE kernels read bf16 banks).
+    """
+    from ..ops import quantize_fp8_weight
+    from .llama import Fp8Pack
+
+    n_packed = 0
+
+    def pack_site(mod, wname: str, pname: str) -> None:
+        nonlocal n_packed
+        w = getattr(mod, wname, None)
+        if w is None or w.dim() != 2 or w.numel() == 0:
+            return
+        N, K = w.shape
+        if N % 128 or K % 128:
+            return
+        setattr(mod, pname, Fp8Pack(*quantize_fp8_weight(w.data)))
+        w.data = torch.empty(0, dtype=w.dtype, device=w.device)
+        n_packed += 1
+
+    for layer in model.layers:
+        if not model.spec.kv_lora_rank:
+            pack_site(layer.attn, "qkv_w", "qkv_pack")
+            pack_site(layer.attn, "o_w", "o_pack")
+        if not hasattr(layer.mlp, "router_w"):
+            pack_site(layer.mlp, "gate_up_w", "gate_up_pack")
+            pack_site(layer.mlp, "down_w", "down_pack")
+    if model.device.type == "cuda":
+        torch.cuda.empty_cache()
+    return n_packed

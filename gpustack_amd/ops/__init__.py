@@ -350,4 +350,123 @@ def mfma_probe(a, b):
     return _load_hip().mfma_probe(a, b)
 
 
+# --- FP8 runtime (dynamic W8A8, OCP e4m3fn; format: torch_ref.py) ----------
+
+# fp8_linear sends M <= this to quant + fp8_gemm and larger M to the
+# up-convert + hipBLASLt fallback. scripts/bench_fp8_gemm.py on MI355X
+# (profiles/fp8_runtime.md): the kernel path beat the fallback on all four
+# Llama-3-8B projections at every measured M from 1 to 16384, by 5-81 %
+# against a spread of at most 4 %; the margin narrows with M, and nothing
+# above 16384 was measured. GPUSTACK_AMD_FP8_KERNEL=0/1 forces the
+# fallback / the kernel for every M.
+FP8_KERNEL_MAX_M = 16384
+
+
+def quantize_fp8_weight(w):
+    """w [N, K] bf16/f32 -> (float8_e4m3fn codes [N, K], f32 scales [N]).
+    Load-time only; runs the reference definition on w's device."""
+    return torch_ref.quantize_fp8_weight(w)
+
+
+def fp8_quant_rows(x, xq=None, xs=None):
+    """Per-row dynamic quantization of x [M, K] -> (xq e4m3fn, xs f32 [M])."""
+    M, K = x.shape
+    if xq is None:
+        xq = torch.empty(M, K, dtype=torch.float8_e4m3fn, device=x.device)
+    if xs is None:
+        xs = torch.empty(M, dtype=torch.float32, device=x.device)
+    hip = _backend(x)
+    if hip is not None:
+        hip.fp8_quant_rows(xq, xs, x)
+    else:
+        torch_ref.fp8_quant_rows(xq, xs, x)
+    return xq, xs
+
+
+def fp8_dequant(q, out=None):
+    """Exact e4m3 -> bf16 up-conversion (no scale)."""
+    if out is None:
+        out = torch.empty(q.shape, dtype=torch.bfloat16, device=q.device)
+    hip = _backend(q)
+    if hip is not None:
+        hip.fp8_dequant(out, q)
+    else:
+        torch_ref.fp8_dequant(out, q)
+    return out
+
+
+def fp8_gemm_splitk(M: int, N: int, K: int) -> int:
+    """Widest split of K (at most 8 ways) that still fits the grid in one
+    wave of blocks: one 256-row-tile block per CU (96 KiB LDS each), two of
+    the 64-row-tile blocks (48 KiB). Matches the measured best split at
+    26 of the 28 points of the scripts/bench_fp8_gemm.py sweep and is
+    within 3 % of it at the other two."""
+    blocks = ((M + 63) // 64 if M <= 64 else (M + 255) // 256) * (N // 128)
+    limit = 512 if M <= 64 else 256
+    splitk = 1
+    while (blocks * splitk * 2 <= limit and splitk < 8
+           and K % (128 * splitk * 2) == 0):
+        splitk *= 2
+    return splitk
+
+
+def fp8_gemm(xq, xs, wq, ws, out=None, splitk: int | None = None):
+    """out[M,N] bf16 = (xq[M,K] @ wq[N,K]^T) * xs[:,None] * ws[None,:],
+    f32 accumulate. The HIP kernel needs N%128==0 and K%(128*splitk)==0
+    and raises otherwise."""
+    M, K = xq.shape
+    N = wq.shape[0]
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=xq.device)
+    hip = _backend(xq)
+    if hip is None:
+        torch_ref.fp8_gemm(out, xq, xs, wq, ws)
+        return out
+    if splitk is None:
+        splitk = fp8_gemm_splitk(M, N, K)
+    wsp = None
+    if splitk > 1:
+        # A captured graph keeps pointing at its workspace, so buffers are
+        # never freed or resized. fp8_gemm_splitk keeps splitk*M*N within
+        # one wave of tiles (<= 256*256*128 floats, 32 MiB): those calls
+        # share one buffer per device (calls on a stream are ordered);
+        # a larger explicit split gets a buffer of its own size class.
+        need = splitk * M * N
+        shared = 256 * 256 * 128
+        size = shared if need <= shared else 1 << (need - 1).bit_length()
+        key = ("fp8", size, xq.device.index)
+        wsp = _SG_WORKSPACES.get(key)
+        if wsp is None:
+            wsp = torch.empty(size, dtype=torch.float32, device=xq.device)
+            _SG_WORKSPACES[key] = wsp
+    hip.fp8_gemm(out, xq, xs, wq, ws, wsp, splitk)
+    return out
+
+
+def fp8_linear(x, qw, ws, bias=None):
+    """Dynamic W8A8 linear: quantize x per token, multiply by the e4m3
+    weight. GPU: M <= FP8_KERNEL_MAX_M runs fp8_gemm; larger M up-converts
+    both code tensors to transient bf16 (exact) for hipBLASLt and scales
+    the result, which costs one extra bf16 rounding. Same xq/wq either way."""
+    hip = _backend(x)
+    if hip is None:
+        return torch_ref.fp8_linear(x, qw, ws, bias)
+    import torch.nn.functional as F
+
+    xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
+    xq, xs = fp8_quant_rows(xb.contiguous())
+    M = xq.shape[0]
+    force = os.environ.get("GPUSTACK_AMD_FP8_KERNEL")
+    if force == "1" or (force != "0" and M <= FP8_KERNEL_MAX_M):
+        out = fp8_gemm(xq, xs, qw, ws)
+    else:
+        out = F.linear(fp8_dequant(xq), fp8_dequant(qw))
+        hip.fp8_scale_out(out, xs, ws)
+    if out.dtype != x.dtype:
+        out = out.to(x.dtype)
+    if bias is not None:
+        out += bias
+    return out
+
+
 build_cos_sin_cache = torch_ref.build_cos_sin_cache

@@ -25,6 +25,11 @@ void moe_gate_up_silu_launch(void*, const void*, const void*, const int*, const 
 void moe_down_scale_launch(void*, const void*, const void*, const int*, const int*, const int*, const float*, const void*, int, int, int, int*, hipStream_t);
 void w4_gemm_launch(void*, const void*, const void*, const void*, const void*, int, int, int, int*, hipStream_t);
 void w4_dequant_launch(void*, const void*, const void*, const void*, long, int, int*, hipStream_t);
+void fp8_gemm_launch(void*, const void*, const void*, const void*, const void*, void*, int, int, int, int, int*, hipStream_t);
+void fp8_quant_rows_launch(void*, void*, const void*, int, int, int*, hipStream_t);
+void fp8_dequant_launch(void*, const void*, long, hipStream_t);
+void fp8_scale_out_launch(void*, const void*, const void*, long, int, int*, hipStream_t);
+void fp8_mfma_probe_launch(float*, const void*, const void*, hipStream_t);
 
 #define HIP_CHECK_LAST()                                                     \
   do {                                                                       \
@@ -405,6 +410,90 @@ void w4_dequant(at::Tensor out, at::Tensor qw, at::Tensor sc, at::Tensor zs) {
   HIP_CHECK_LAST();
 }
 
+void check_fp8(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == at::kFloat8_e4m3fn, name,
+              " must be float8_e4m3fn");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+void check_f32(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be f32");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+void fp8_quant_rows(at::Tensor xq, at::Tensor xs, at::Tensor x) {
+  check_fp8(xq, "xq"); check_f32(xs, "xs"); check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2 && xq.dim() == 2);
+  const int M = x.size(0), K = x.size(1);
+  TORCH_CHECK(xq.size(0) == M && xq.size(1) == K && xs.numel() == M);
+  int err = 0;
+  fp8_quant_rows_launch(xq.data_ptr(), xs.data_ptr(), x.data_ptr(), M, K,
+                        &err, cur_stream(x));
+  TORCH_CHECK(!err, "fp8_quant_rows: unsupported shape M=", M, " K=", K,
+              " (need M>=1, K%8==0)");
+  HIP_CHECK_LAST();
+}
+
+void fp8_gemm(at::Tensor out, at::Tensor xq, at::Tensor xs, at::Tensor wq,
+              at::Tensor ws, c10::optional<at::Tensor> workspace,
+              long splitk) {
+  check_bf16(out, "out"); check_fp8(xq, "xq"); check_fp8(wq, "wq");
+  check_f32(xs, "xs"); check_f32(ws, "ws");
+  TORCH_CHECK(xq.dim() == 2 && wq.dim() == 2 && out.dim() == 2);
+  const int M = xq.size(0), K = xq.size(1), N = wq.size(0);
+  TORCH_CHECK(wq.size(1) == K && out.size(0) == M && out.size(1) == N);
+  TORCH_CHECK(xs.numel() == M && ws.numel() == N);
+  void* wsp = nullptr;
+  if (splitk > 1) {
+    TORCH_CHECK(workspace.has_value(), "splitk>1 needs an f32 workspace");
+    check_f32(*workspace, "workspace");
+    TORCH_CHECK(workspace->numel() >= (long)splitk * M * N,
+                "workspace too small");
+    wsp = workspace->data_ptr();
+  }
+  int err = 0;
+  fp8_gemm_launch(out.data_ptr(), xq.data_ptr(), xs.data_ptr(),
+                  wq.data_ptr(), ws.data_ptr(), wsp, M, N, K, (int)splitk,
+                  &err, cur_stream(xq));
+  TORCH_CHECK(!err, "fp8_gemm: unsupported shape M=", M, " N=", N, " K=", K,
+              " splitk=", splitk, " (need N%128==0, K%(128*splitk)==0)");
+  HIP_CHECK_LAST();
+}
+
+void fp8_dequant(at::Tensor out, at::Tensor q) {
+  check_bf16(out, "out"); check_fp8(q, "q");
+  TORCH_CHECK(out.numel() == q.numel());
+  fp8_dequant_launch(out.data_ptr(), q.data_ptr(), (long)q.numel(),
+                     cur_stream(q));
+  HIP_CHECK_LAST();
+}
+
+void fp8_scale_out(at::Tensor out, at::Tensor xs, at::Tensor ws) {
+  check_bf16(out, "out"); check_f32(xs, "xs"); check_f32(ws, "ws");
+  TORCH_CHECK(out.dim() == 2);
+  const long M = out.size(0);
+  const int N = out.size(1);
+  TORCH_CHECK(xs.numel() == M && ws.numel() == N);
+  int err = 0;
+  fp8_scale_out_launch(out.data_ptr(), xs.data_ptr(), ws.data_ptr(), M, N,
+                       &err, cur_stream(out));
+  TORCH_CHECK(!err, "fp8_scale_out: unsupported shape M=", M, " N=", N,
+              " (need N%8==0)");
+  HIP_CHECK_LAST();
+}
+
+at::Tensor fp8_mfma_probe(at::Tensor a, at::Tensor b) {
+  check_fp8(a, "a"); check_fp8(b, "b");
+  TORCH_CHECK(a.numel() == 16 * 32 && b.numel() == 32 * 16);
+  auto d = at::zeros({16, 16}, a.options().dtype(at::kFloat));
+  fp8_mfma_probe_launch(d.data_ptr<float>(), a.data_ptr(), b.data_ptr(),
+                        cur_stream(a));
+  HIP_CHECK_LAST();
+  return d;
+}
+
 void gemm_lab(at::Tensor out, at::Tensor x, at::Tensor w, long mode) {
   check_bf16(out, "out"); check_bf16(x, "x"); check_bf16(w, "w");
   const int M = x.size(0), K = x.size(1), N = w.size(0);
@@ -474,4 +563,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "W4A16 GEMM: packed-int4 weights dequantized in-register");
   m.def("w4_dequant", &w4_dequant,
         "packed-int4 -> bf16 weight expansion (prefill transient)");
+  m.def("fp8_quant_rows", &fp8_quant_rows,
+        "per-row dynamic e4m3 quantization (codes + f32 scale per row)");
+  m.def("fp8_gemm", &fp8_gemm,
+        "W8A8 e4m3 GEMM, f32 accumulate, per-row x per-column scales");
+  m.def("fp8_dequant", &fp8_dequant, "exact e4m3 -> bf16 up-conversion");
+  m.def("fp8_scale_out", &fp8_scale_out,
+        "in-place out[m,n] *= xs[m]*ws[n] (W8A8 fallback epilogue)");
+  m.def("fp8_mfma_probe", &fp8_mfma_probe,
+        "16x16x32 fp8 MFMA layout probe");
 }

@@ -415,3 +415,58 @@ def paged_prefill_attn(
         att = _sink_softmax(att, sinks)
         out[start:start + new] = (att @ vals).permute(1, 0, 2).to(out.dtype)
         row += new
+
+
+# --- FP8 runtime (dynamic W8A8, OCP e4m3fn) ---------------------------------
+#
+# Row format shared by weights (per output channel) and activations (per
+# token): scale = amax|row| / 448 in f32 (1.0 for an all-zero row), code =
+# e4m3fn_rne(clamp(row / scale, -448, 448)). True f32 division on both the
+# scale and the quotient, never a reciprocal multiply, so the host reference
+# and the HIP kernel agree bit for bit. The clamp comes before the convert:
+# torch's cast gives NaN above 464 instead of saturating.
+
+FP8_MAX = 448.0
+
+
+def fp8_quant_rows(xq: torch.Tensor, xs: torch.Tensor, x: torch.Tensor) -> None:
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    xs.copy_(scale)
+    xq.copy_((xf / scale.unsqueeze(-1)).clamp(-FP8_MAX, FP8_MAX)
+             .to(torch.float8_e4m3fn))
+
+
+def quantize_fp8_weight(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """w [N, K] bf16/f32 -> (e4m3fn codes [N, K], f32 scales [N])."""
+    qw = torch.empty(w.shape, dtype=torch.float8_e4m3fn, device=w.device)
+    ws = torch.empty(w.shape[0], dtype=torch.float32, device=w.device)
+    fp8_quant_rows(qw, ws, w)
+    return qw, ws
+
+
+def fp8_dequant(out: torch.Tensor, q: torch.Tensor) -> None:
+    """Exact up-conversion of e4m3 codes (no scale)."""
+    out.copy_(q.float())
+
+
+def fp8_gemm(out: torch.Tensor, xq: torch.Tensor, xs: torch.Tensor,
+             wq: torch.Tensor, ws: torch.Tensor) -> None:
+    """out[m,n] = (sum_k xq[m,k] wq[n,k]) * xs[m] * ws[n], f32 accumulate,
+    one rounding to out.dtype."""
+    acc = xq.float() @ wq.float().t()
+    out.copy_(acc * xs.float().unsqueeze(1) * ws.float().unsqueeze(0))
+
+
+def fp8_linear(x: torch.Tensor, qw: torch.Tensor, ws: torch.Tensor,
+               bias: torch.Tensor | None = None) -> torch.Tensor:
+    M, K = x.shape
+    xq = torch.empty(M, K, dtype=torch.float8_e4m3fn, device=x.device)
+    xs = torch.empty(M, dtype=torch.float32, device=x.device)
+    fp8_quant_rows(xq, xs, x)
+    out = torch.empty(M, qw.shape[0], dtype=x.dtype, device=x.device)
+    fp8_gemm(out, xq, xs, qw, ws)
+    if bias is not None:
+        out += bias
+    return out

@@ -81,12 +81,34 @@ def model_spec_for(model: Model | dict) -> ModelSpec | None:
 def _weight_bytes(model: dict, spec: ModelSpec, tp: int) -> int:
     """Per-shard resident weight bytes, accounting for runtime W4 packing
     (backend_parameters quantize_runtime=w4 keeps weights int4: ~0.28x of
-    bf16 incl. scales) and the bf16 default."""
+    bf16 incl. scales), runtime FP8 and the bf16 default.
+
+    quantize_runtime=fp8 on a dense spec: embeddings and lm_head stay bf16
+    at full size, everything else is halved, plus 4 B per output row of the
+    packed projections for the f32 scales. MoE specs get no reduction
+    (expert banks stay bf16; the claim must never fall below what stays
+    resident)."""
     bp = model.get("backend_parameters") or {}
     w = spec.weight_bytes() // tp
     if bp.get("quantize_runtime") == "w4":
         w = int(w * 0.28)
+    elif (bp.get("quantize_runtime") == "fp8" and spec.num_experts == 0
+          and not spec.kv_lora_rank):
+        w = fp8_weight_bytes(spec) // tp
     return w
+
+
+def fp8_weight_bytes(spec: ModelSpec) -> int:
+    """Resident bytes of a dense spec under quantize_runtime=fp8 (all
+    shards together)."""
+    total = spec.weight_bytes()
+    emb = (spec.vocab_size * spec.hidden_size
+           * (1 if spec.tie_word_embeddings else 2)) * 2
+    # output rows of qkv, o, gate_up, down per layer
+    rows = ((spec.num_heads + 2 * spec.num_kv_heads) * spec.head_dim
+            + spec.hidden_size + 2 * spec.intermediate_size
+            + spec.hidden_size) * spec.num_layers
+    return emb + (total - emb) // 2 + 4 * rows
 
 
 def estimate_vram_claim(model: Model | dict, spec: ModelSpec | None, tp: int) -> int:
