@@ -276,6 +276,27 @@ def paged_prefill_attn(out, q, k_cache, v_cache, block_tables,
 
 
 _SG_WORKSPACES: dict = {}
+_SPLITK_SHARED_FLOATS = 256 * 256 * 128
+
+
+def _splitk_workspace(need_floats: int, device):
+    """f32 [S, M, N] partials for skinny_gemm and fp8_gemm. A captured
+    graph keeps pointing at its workspace, so buffers are never freed or
+    resized. fp8_gemm_splitk keeps splitk*M*N within one wave of tiles
+    (<= 256*256*128 floats, 32 MiB): such calls share one buffer per device
+    (calls on a stream are ordered); a larger request (the down_proj split
+    of skinny_gemm at M > 512, an explicit split) gets the buffer of its
+    power-of-two size class."""
+    device = torch.device(device)
+    size = _SPLITK_SHARED_FLOATS
+    if need_floats > size:
+        size = 1 << (need_floats - 1).bit_length()
+    key = (size, device.type, device.index)
+    ws = _SG_WORKSPACES.get(key)
+    if ws is None:
+        ws = torch.empty(size, dtype=torch.float32, device=device)
+        _SG_WORKSPACES[key] = ws
+    return ws
 
 
 def gemm8(x, w, out=None, safe: bool = False):
@@ -316,13 +337,7 @@ def skinny_gemm(x, w, out=None, splitk: int | None = None, version: int = 1):
             splitk *= 2
     if out is None:
         out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-    ws = None
-    if splitk > 1:
-        key = (splitk, M, N, x.device.index)
-        ws = _SG_WORKSPACES.get(key)
-        if ws is None:
-            ws = torch.empty(splitk * M * N, dtype=torch.float32, device=x.device)
-            _SG_WORKSPACES[key] = ws
+    ws = _splitk_workspace(splitk * M * N, x.device) if splitk > 1 else None
     _load_hip().skinny_gemm(out, x, w, ws, splitk, version)
     return out
 
@@ -424,21 +439,7 @@ def fp8_gemm(xq, xs, wq, ws, out=None, splitk: int | None = None):
         return out
     if splitk is None:
         splitk = fp8_gemm_splitk(M, N, K)
-    wsp = None
-    if splitk > 1:
-        # A captured graph keeps pointing at its workspace, so buffers are
-        # never freed or resized. fp8_gemm_splitk keeps splitk*M*N within
-        # one wave of tiles (<= 256*256*128 floats, 32 MiB): those calls
-        # share one buffer per device (calls on a stream are ordered);
-        # a larger explicit split gets a buffer of its own size class.
-        need = splitk * M * N
-        shared = 256 * 256 * 128
-        size = shared if need <= shared else 1 << (need - 1).bit_length()
-        key = ("fp8", size, xq.device.index)
-        wsp = _SG_WORKSPACES.get(key)
-        if wsp is None:
-            wsp = torch.empty(size, dtype=torch.float32, device=xq.device)
-            _SG_WORKSPACES[key] = wsp
+    wsp = _splitk_workspace(splitk * M * N, xq.device) if splitk > 1 else None
     hip.fp8_gemm(out, xq, xs, wq, ws, wsp, splitk)
     return out
 

@@ -68,8 +68,10 @@ def build(verbose: bool = False, force: bool = False) -> Path:
     flags = _common_flags(abi)
 
     objs = []
-    newest_src = 0.0
-    for src in HIP_SOURCES + CPP_SOURCES + ["common.h"]:
+    # every header is a dependency of every object and of the .so
+    newest_hdr = max(p.stat().st_mtime for p in CSRC.glob("*.h"))
+    newest_src = newest_hdr
+    for src in HIP_SOURCES + CPP_SOURCES:
         p = CSRC / src
         if p.exists():
             newest_src = max(newest_src, p.stat().st_mtime)
@@ -85,7 +87,7 @@ def build(verbose: bool = False, force: bool = False) -> Path:
             not force
             and obj.exists()
             and obj.stat().st_mtime >= srcp.stat().st_mtime
-            and obj.stat().st_mtime >= (CSRC / "common.h").stat().st_mtime
+            and obj.stat().st_mtime >= newest_hdr
         ):
             objs.append(str(obj))
             continue

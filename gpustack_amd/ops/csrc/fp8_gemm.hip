@@ -12,183 +12,34 @@
 //  - fp8_dequant:    exact e4m3 -> bf16 up-conversion (large-M fallback)
 //  - fp8_mfma_probe: one wave, one instruction, checks the A/B lane map
 //
-// GEMM structure: the v1 kernel of skinny_gemm.hip with bytes for bf16.
-// BK = 128 fp8 elements keeps an LDS row at 128 B, so the global_load_lds
-// staging and the ((row&7)<<4) XOR swizzle carry over byte for byte.
-//
-// Fragment reads: the fp8 instruction takes 8 B of A and B per lane. Read as
-// ds_read_b64 through the carried-over swizzle, the 32 lanes of a half-wave
-// would touch 16 rows x 2 eight-byte halves; rows r and r+8 have equal
-// (row&7) and equal parity, i.e. the same 16-B slot of the 256-B bank row,
-// so that read is 2-way conflicted (the swizzle only separates 8 rows, which
-// is all a 16-lane ds_read_b128 group needs). Instead each lane keeps the
-// bf16 kernel's conflict-free ds_read_b128 and feeds its low and high 8 B to
-// two consecutive MFMAs. That permutes k inside a 64-byte half-row (lane
-// group g supplies bytes 16g..16g+7 to the first MFMA and 16g+8..16g+15 to
-// the second), identically for A and B, so the dot product is unchanged and
-// the kernel issues half the LDS reads.
-#include "common.h"
+// GEMM structure: the shared split-K tile of splitk_tile.h with the FP8
+// element. BK = 128 fp8 elements keeps an LDS row at 128 B, so the staging
+// and the swizzle are those of the bf16 skinny_gemm v1 byte for byte; why
+// fragments are still read 16 B at a time is explained at the Fp8 policy.
+#include "splitk_tile.h"
 
 namespace {
 
-constexpr int F8_BN = 128;
-constexpr int F8_BK = 128;             // fp8 elements == bytes per LDS row
-constexpr int F8_WAVES = 8;
-constexpr int F8_THREADS = F8_WAVES * WAVE_SIZE;
-constexpr float F8_MAX = 448.f;
+using namespace splitk;
 
-typedef __attribute__((ext_vector_type(2))) long i64x2;
+constexpr float F8_MAX = 448.f;
 
 DEVICE_INLINE f32x4 f8_mfma(long a, long b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, c, 0, 0, 0);
-}
-
-DEVICE_INLINE int f8_swz(int row, int colbyte) {
-  return row * F8_BK + (colbyte ^ ((row & 7) << 4));
 }
 
 // MI = 16-row fragments per wave along M; the block tile is (32*MI) x 128.
 // MI=8 is the 256-row tile of the bf16 kernel; MI=2 (64 rows) serves small
 // decode batches, where a 256-row X tile would triple the staging traffic.
 template <int MI, bool WRITE_PARTIAL>
-__global__ __launch_bounds__(F8_THREADS) void fp8_gemm_kernel(
-    void* __restrict__ out,                  // bf16 [M,N] or f32 [S,M,N]
-    const unsigned char* __restrict__ xq,    // [M, K] e4m3
-    const float* __restrict__ xs,            // [M]
-    const unsigned char* __restrict__ wq,    // [N, K] e4m3
-    const float* __restrict__ ws,            // [N]
+__global__ __launch_bounds__(THREADS) void fp8_gemm_kernel(
+    void* __restrict__ out,            // bf16 [M,N] or f32 [S,M,N]
+    const void* __restrict__ xq,       // [M, K] e4m3
+    const float* __restrict__ xs,      // [M]
+    const void* __restrict__ wq,       // [N, K] e4m3
+    const float* __restrict__ ws,      // [N]
     int M, int N, int K, int splitk) {
-  constexpr int BM = 32 * MI;
-  constexpr int XCHUNKS = BM * F8_BK / 16 / F8_THREADS;   // 16-B chunks/thread
-  static_assert(XCHUNKS >= 1, "X tile must give every thread a chunk");
-  const int mt = (M + BM - 1) / BM;
-  int tid = blockIdx.x;
-  const int split = tid % splitk;
-  tid /= splitk;
-  const int m0 = (tid % mt) * BM;
-  const int n0 = (tid / mt) * F8_BN;
-  const int kchunk = K / splitk;          // multiple of F8_BK (host-checked)
-  const int k0 = split * kchunk;
-  const int nk = kchunk / F8_BK;
-
-  __shared__ unsigned char Xl[2][BM * F8_BK];
-  __shared__ unsigned char Wl[2][F8_BN * F8_BK];
-
-  const int t = threadIdx.x;
-  const int lane = t & (WAVE_SIZE - 1);
-  const int wid = t / WAVE_SIZE;
-  const int wm = wid >> 2;                // 0..1  (row half)
-  const int wn = wid & 3;                 // 0..3  (col quarter)
-  const int lc = lane & 15;
-  const int lg = lane >> 4;
-
-  // linear LDS byte L of a 16-B chunk maps to logical (row = L/128,
-  // colbyte = (L%128) ^ swz(row)); the global source reads that element.
-  auto stage = [&](int buf, int kb) {
-    const long kbase = k0 + (long)kb * F8_BK;
-#pragma unroll
-    for (int r = 0; r < XCHUNKS; ++r) {
-      const int L = (t + r * F8_THREADS) * 16;
-      const int row = L / F8_BK;
-      const int colbyte = (L % F8_BK) ^ ((row & 7) << 4);
-      int grow = m0 + row;
-      if (grow >= M) grow = M - 1;        // clamp (masked at write)
-      const unsigned char* src = xq + (long)grow * K + kbase + colbyte;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)src,
-          (__attribute__((address_space(3))) unsigned int*)(Xl[buf] + L),
-          16, 0, 0);
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int L = (t + r * F8_THREADS) * 16;
-      const int row = L / F8_BK;
-      const int colbyte = (L % F8_BK) ^ ((row & 7) << 4);
-      const unsigned char* src = wq + (long)(n0 + row) * K + kbase + colbyte;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)src,
-          (__attribute__((address_space(3))) unsigned int*)(Wl[buf] + L),
-          16, 0, 0);
-    }
-  };
-
-  f32x4 acc[MI][2];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  stage(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  int buf = 0;
-  for (int kb = 0; kb < nk; ++kb) {
-    if (kb + 1 < nk) stage(buf ^ 1, kb + 1);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {          // 64-byte half-row = 2 k-steps
-      const int colbyte = h * 64 + lg * 16;
-      i64x2 bfrag[2];
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        const int row = wn * 32 + ni * 16 + lc;       // W row (output col)
-        bfrag[ni] = *reinterpret_cast<const i64x2*>(
-            Wl[buf] + f8_swz(row, colbyte));
-      }
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) {
-        const int row = wm * (16 * MI) + mi * 16 + lc;  // X row (output row)
-        const i64x2 a = *reinterpret_cast<const i64x2*>(
-            Xl[buf] + f8_swz(row, colbyte));
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          acc[mi][ni] = f8_mfma(a[0], bfrag[ni][0], acc[mi][ni]);
-          acc[mi][ni] = f8_mfma(a[1], bfrag[ni][1], acc[mi][ni]);
-        }
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    buf ^= 1;
-  }
-
-  // epilogue: D row = (l>>4)*4 + r, col = l&15 per 16x16 fragment. The
-  // scales multiply the f32 sum before the single bf16 rounding; with
-  // split-K the reduce kernel does that on the final sum instead.
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int gcol = n0 + wn * 32 + ni * 16 + lc;
-    const float wsc = WRITE_PARTIAL ? 1.f : ws[gcol];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int grow = m0 + wm * (16 * MI) + mi * 16 + lg * 4 + r;
-        if (grow >= M) continue;
-        if (WRITE_PARTIAL) {
-          reinterpret_cast<float*>(out)[((long)split * M + grow) * N + gcol] =
-              acc[mi][ni][r];
-        } else {
-          reinterpret_cast<unsigned short*>(out)[(long)grow * N + gcol] =
-              f2bf(acc[mi][ni][r] * xs[grow] * wsc);
-        }
-      }
-    }
-  }
-}
-
-// partial[S, M, N] f32 -> out[M, N] bf16; fixed summation order, no atomics
-__global__ void fp8_reduce_kernel(unsigned short* __restrict__ out,
-                                  const float* __restrict__ partial,
-                                  const float* __restrict__ xs,
-                                  const float* __restrict__ ws,
-                                  long MN, int N, int splitk) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < MN;
-       i += (long)gridDim.x * blockDim.x) {
-    float a = 0.f;
-    for (int s = 0; s < splitk; ++s) a += partial[s * MN + i];
-    out[i] = f2bf(a * xs[i / N] * ws[i % N]);
-  }
+  tile_body<Fp8, MI, WRITE_PARTIAL>(out, xq, xs, wq, ws, M, N, K, splitk);
 }
 
 // ---------------------------------------------------------------------------
@@ -328,51 +179,27 @@ __global__ void fp8_mfma_probe_kernel(float* __restrict__ d,
   for (int r = 0; r < 4; ++r) d[(lg * 4 + r) * 16 + lc] = c[r];
 }
 
-template <int MI>
-void fp8_gemm_dispatch(void* out, const unsigned char* xq, const float* xs,
-                       const unsigned char* wq, const float* ws,
-                       void* workspace, int M, int N, int K, int splitk,
-                       hipStream_t s) {
-  constexpr int BM = 32 * MI;
-  const int mt = (M + BM - 1) / BM;
-  const int nt = N / F8_BN;
-  dim3 grid(mt * nt * splitk);
-  dim3 block(F8_THREADS);
-  if (splitk > 1) {
-    hipLaunchKernelGGL((fp8_gemm_kernel<MI, true>), grid, block, 0, s,
-                       workspace, xq, xs, wq, ws, M, N, K, splitk);
-    const long MN = (long)M * N;
-    int rgrid = (int)((MN + 255) / 256);
-    if (rgrid > 2048) rgrid = 2048;
-    hipLaunchKernelGGL(fp8_reduce_kernel, dim3(rgrid), dim3(256), 0, s,
-                       (unsigned short*)out, (const float*)workspace, xs, ws,
-                       MN, N, splitk);
-  } else {
-    hipLaunchKernelGGL((fp8_gemm_kernel<MI, false>), grid, block, 0, s, out,
-                       xq, xs, wq, ws, M, N, K, splitk);
-  }
-}
-
 }  // namespace
 
 void fp8_gemm_launch(void* out, const void* xq, const void* xs,
                      const void* wq, const void* ws, void* workspace, int M,
                      int N, int K, int splitk, int* err_unsupported,
                      hipStream_t s) {
-  const bool ok = M >= 1 && N >= F8_BN && N % F8_BN == 0 && splitk >= 1 &&
-                  splitk <= 16 && K >= F8_BK * splitk &&
-                  K % (F8_BK * splitk) == 0 &&
+  constexpr int BK = ROW_BYTES / Fp8::ES;
+  const bool ok = M >= 1 && N >= BN && N % BN == 0 && splitk >= 1 &&
+                  splitk <= 16 && K >= BK * splitk &&
+                  K % (BK * splitk) == 0 &&
                   (splitk == 1 || workspace != nullptr);
   *err_unsupported = !ok;
   if (!ok) return;
   if (M <= 64) {
-    fp8_gemm_dispatch<2>(out, (const unsigned char*)xq, (const float*)xs,
-                         (const unsigned char*)wq, (const float*)ws,
+    launch<64, BN, true>(fp8_gemm_kernel<2, true>, fp8_gemm_kernel<2, false>,
+                         out, xq, (const float*)xs, wq, (const float*)ws,
                          workspace, M, N, K, splitk, s);
   } else {
-    fp8_gemm_dispatch<8>(out, (const unsigned char*)xq, (const float*)xs,
-                         (const unsigned char*)wq, (const float*)ws,
-                         workspace, M, N, K, splitk, s);
+    launch<256, BN, true>(fp8_gemm_kernel<8, true>, fp8_gemm_kernel<8, false>,
+                          out, xq, (const float*)xs, wq, (const float*)ws,
+                          workspace, M, N, K, splitk, s);
   }
 }
 

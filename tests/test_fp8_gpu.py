@@ -88,6 +88,24 @@ def test_fp8_gemm_exact(shape, splitk):
     assert torch.equal(out.cpu(), ref.to(torch.bfloat16))
 
 
+@pytest.mark.parametrize("splitk", [1, 2, 4])
+def test_fp8_gemm_matches_skinny_on_integer_codes(splitk):
+    """fp8_gemm and skinny_gemm v1 are one tile body with two element types:
+    the same integer matrices, as e4m3 codes with unit scales and as bf16,
+    give bit-equal outputs. Integers keep every partial sum exact; with
+    general values the two element types tile K differently and may differ
+    in the last bit."""
+    M, N, K = SHAPES[3]
+    g = torch.Generator().manual_seed(11 + splitk)
+    x = torch.randint(-4, 5, (M, K), generator=g).float().cuda()
+    w = torch.randint(-4, 5, (N, K), generator=g).float().cuda()
+    out8 = ops.fp8_gemm(x.to(F8), torch.ones(M, device="cuda"), w.to(F8),
+                        torch.ones(N, device="cuda"), splitk=splitk)
+    out16 = ops.skinny_gemm(x.to(torch.bfloat16), w.to(torch.bfloat16),
+                            splitk=splitk, version=1)
+    assert torch.equal(out8, out16)
+
+
 def _bound(ref, xq, xs, wq, ws, extra_roundings=0):
     K = xq.shape[1]
     S = (xq.double().abs() @ wq.double().abs().t()) \

@@ -4,6 +4,7 @@ Every op the engine uses on the hot path is checked here against
 gpustack_amd.ops.torch_ref with random (asymmetric) inputs — including the
 MFMA fragment-layout probe (guide G9: transpose-detecting checks).
 """
+import functools
 import math
 
 import pytest
@@ -242,6 +243,40 @@ def test_skinny_gemm(M, N, K, splitk, version):
     assert torch.allclose(got.float(), ref, atol=0.5, rtol=3e-2), (
         (got.float() - ref).abs().max().item()
     )
+
+
+_EXACT_SHAPES = [
+    (1, 256, 256),       # single row
+    (17, 256, 512),      # partial tile
+    (257, 256, 1024),    # one row past a 256-row tile: clamped loads,
+                         # guarded stores, two m-tiles
+    (300, 384, 1024),    # v1 only: N not a multiple of 256
+]
+_EXACT_CASES = [(shape, splitk, version)
+                for shape in _EXACT_SHAPES for splitk in (1, 2, 4)
+                for version in (1, 2)
+                if shape[2] % (64 * splitk) == 0
+                and (version == 1 or shape[1] % 256 == 0)]
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_gemm_case(M, N, K):
+    """Integer-valued bf16 in [-4, 4]: every partial sum is exact in f32 for
+    K <= 1024 (|sum| <= 16 K < 2^24), in any order."""
+    g = torch.Generator().manual_seed(M + 31 * N + 977 * K)
+    x = torch.randint(-4, 5, (M, K), generator=g).to(torch.bfloat16)
+    w = torch.randint(-4, 5, (N, K), generator=g).to(torch.bfloat16)
+    ref = (x.double() @ w.double().t()).to(torch.bfloat16)
+    return x.cuda(), w.cuda(), ref
+
+
+@pytest.mark.parametrize("shape,splitk,version", _EXACT_CASES)
+def test_skinny_gemm_exact(shape, splitk, version):
+    """Bit-equal to the f64 product rounded once to bf16: a swapped fragment
+    or a wrong clamped row cannot hide inside a tolerance."""
+    x, w, ref = _exact_gemm_case(*shape)
+    got = ops.skinny_gemm(x, w, splitk=splitk, version=version)
+    assert torch.equal(got.cpu(), ref)
 
 
 @pytest.mark.parametrize("lens", [[17, 5, 160], [2048]])

@@ -170,3 +170,25 @@ def test_yarn_rope_matches_hf():
     freqs = torch.outer(t, inv.float())
     ref = torch.cat([freqs.cos(), freqs.sin()], -1) * att
     assert (cache - ref).abs().max().item() < 1e-4
+
+
+def test_splitk_workspace_size_classes():
+    """One shared buffer per device up to 256*256*128 floats, power-of-two
+    classes above; a repeat call allocates nothing."""
+    from gpustack_amd import ops
+
+    shared = 256 * 256 * 128
+    a = ops._splitk_workspace(4 * 64 * 4096, "cpu")
+    assert a.dtype == torch.float32 and a.numel() == shared
+    assert ops._splitk_workspace(shared, "cpu") is a
+    big = ops._splitk_workspace(shared + 1, "cpu")
+    assert big is not a and big.numel() == 2 * shared
+    need = 3 * shared + 5
+    c = ops._splitk_workspace(need, "cpu")
+    assert c.numel() >= need and c.numel() & (c.numel() - 1) == 0
+    n_buffers = len(ops._SG_WORKSPACES)
+    assert ops._splitk_workspace(need, "cpu") is c
+    assert ops._splitk_workspace(4 * shared, "cpu") is c
+    assert ops._splitk_workspace(1, "cpu") is a
+    assert len(ops._SG_WORKSPACES) == n_buffers
+
