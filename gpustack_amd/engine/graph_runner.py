@@ -18,6 +18,7 @@ import os
 
 import torch
 
+from .. import ops
 from ..models.llama import ForwardMeta
 from .scheduler import ScheduledBatch
 
@@ -36,6 +37,9 @@ class DecodeGraphRunner:
         dev = runner.device
         spec = getattr(cfg, "speculative", None)
         rps = 1 + int(spec.get("num_draft_tokens", 3)) if spec else 1
+        # one row per sequence: the captured step may fold rope and the
+        # cache write into the attention kernel (read at capture time)
+        self.fused_decode = rps == 1 and ops.fused_decode_enabled()
         self.max_bs = min(cfg.max_num_seqs * rps, BUCKETS[-1])
         self.buckets = [b for b in BUCKETS if b <= self.max_bs]
         if self.buckets[-1] != self.max_bs:
@@ -86,6 +90,7 @@ class DecodeGraphRunner:
             logits_indices=self.logits_idx[:bs],
             block_tables=self.block_tables[:bs],
             seq_lens=self.seq_lens[:bs],
+            fused_decode=self.fused_decode,
         )
 
     def capture(self) -> None:

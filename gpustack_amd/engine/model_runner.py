@@ -740,6 +740,11 @@ class ModelRunner:
                 logits_indices=torch.arange(nrows, dtype=torch.long, device=dev),
                 block_tables=bt.to(dev),
                 seq_lens=torch.tensor(batch.seq_lens, dtype=torch.int32, device=dev),
+                # one new token per distinct sequence (this branch is never
+                # prefill, suffix, mixed or CP)
+                fused_decode=(rps == 1
+                              and getattr(self.cfg, "speculative", None) is None
+                              and ops.fused_decode_enabled()),
             )
         slots = self._row_lora_slots(batch)
         if slots is not None:

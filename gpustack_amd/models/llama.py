@@ -55,6 +55,11 @@ class ForwardMeta:
     # sequences (slot_mapping is then the full-batch mapping, positions
     # stay local-row)
     cp: object | None = None
+    # plain decode step: every row is the one new token of a distinct
+    # sequence (no speculative rows, suffix rows, mixed batch or CP), so
+    # attention layers may fold rope and the cache write into the decode
+    # kernel (ops.paged_attn_decode_fused)
+    fused_decode: bool = False
 
 
 class W4Pack:
@@ -206,6 +211,15 @@ class Attention(nn.Module):
             else:
                 ops.rms_norm(q.view(-1, self.d), q.view(-1, self.d), self.q_norm, self.spec.rms_norm_eps)
                 ops.rms_norm(k.view(-1, self.d), k.view(-1, self.d), self.k_norm, self.spec.rms_norm_eps)
+        if self._fuses_decode(meta, k_cache):
+            # rope, cache write and attention in one kernel; nothing below
+            # reads the roped q/k back from the qkv buffer
+            out = torch.empty(T, self.hq, self.d, dtype=q.dtype, device=q.device)
+            ops.paged_attn_decode_fused(
+                out, q, k, v, k_cache, v_cache, meta.positions, cos_sin,
+                meta.slot_mapping, meta.block_tables, meta.seq_lens,
+                self.scale)
+            return self._o_proj(out, meta)
         if self.use_rope:
             ops.rotary_embedding(meta.positions, q, k, cos_sin, self.d,
                                  self.rot_dim, mode=self.spec.rope_mode)
@@ -253,10 +267,32 @@ class Attention(nn.Module):
                 out, q, k_cache, v_cache, meta.block_tables, meta.seq_lens,
                 self.scale, **sw
             )
+        return self._o_proj(out, meta)
+
+    def _o_proj(self, out, meta: ForwardMeta):
+        T = out.shape[0]
         o = qlinear(out.view(T, -1), self.o_w, self.o_pack, self.o_b)
         if meta.lora is not None:
             meta.lora.apply(self.layer_idx, out.view(T, -1), o, self._o_projs)
         return self.comm.all_reduce(o)
+
+    def _fuses_decode(self, meta: ForwardMeta, k_cache) -> bool:
+        """The fused decode kernel covers the plain llama-lineage layer:
+        full NeoX rotary at head_dim 128, bf16 KV, no qk-norm and none of
+        the sink / window / softcap variants, at the GQA ratios where it
+        measured a gain. Everything else runs the separate ops."""
+        return (meta.fused_decode
+                and self.use_rope
+                and self.spec.rope_mode == "neox"
+                and self.rot_dim == self.d == 128
+                and not self.spec.qk_norm
+                and self.sinks is None and not self.window
+                and not self.softcap
+                and (k_cache.dtype == torch.bfloat16 if k_cache.is_cuda
+                     else k_cache.dtype != torch.float8_e4m3fn)
+                # the kernel covers GQ 1-8; taken where it measured faster
+                # than the three launches (profiles/decode_fused.md)
+                and self.hq // self.hkv in (1, 2, 4))
 
     def _full_qk_norm(self, q, k):
         """OLMo-2 full-projection RMSNorm: the mean square runs over ALL

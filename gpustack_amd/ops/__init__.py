@@ -186,6 +186,37 @@ def paged_attn_decode(out, q, k_cache, v_cache, block_tables, seq_lens,
                                     window=window, softcap=softcap)
 
 
+def fused_decode_enabled() -> bool:
+    """GPUSTACK_AMD_FUSED_DECODE=0 keeps the plain decode step on the three
+    separate ops (rope, cache write, attention); default on."""
+    return os.environ.get("GPUSTACK_AMD_FUSED_DECODE", "1") != "0"
+
+
+def paged_attn_decode_fused(out, q, k, v, k_cache, v_cache, positions,
+                            cos_sin, slot_mapping, block_tables, seq_lens,
+                            scale: float) -> None:
+    """rotary_embedding (neox, rot_dim == head_dim) -> reshape_and_cache ->
+    paged_attn_decode for a plain decode step — every row the one new token
+    of a distinct sequence — in one kernel. q/k/v are the UNROPED views of
+    the qkv buffer; unlike rotary_embedding this leaves them as they are
+    (only the pools and `out` are written). bf16 pools, head_dim 128.
+    Covers GQ 1-8, but only pays at GQ 1, 2 and 4 (what the model takes): at
+    GQ 5-7 it measured no faster than the three ops and at GQ 8 a third
+    slower (profiles/decode_fused.md)."""
+    hip = _backend(q)
+    if hip is not None:
+        hip.paged_attn_decode_fused(out, q, k, v, k_cache, v_cache, positions,
+                                    cos_sin, slot_mapping, block_tables,
+                                    seq_lens, scale)
+    else:
+        d = q.shape[-1]
+        q, k = q.clone(), k.clone()
+        torch_ref.rotary_embedding(positions, q, k, cos_sin, d, d)
+        torch_ref.reshape_and_cache(k, v, k_cache, v_cache, slot_mapping)
+        torch_ref.paged_attn_decode(out, q, k_cache, v_cache, block_tables,
+                                    seq_lens, scale)
+
+
 def mla_decode(ctx_out, q_cat, lat_cache, block_tables, seq_lens,
                scale: float) -> None:
     """MLA absorbed decode (DeepSeek): ctx_out[N,H,512] f32 = softmax

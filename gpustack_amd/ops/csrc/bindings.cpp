@@ -14,6 +14,7 @@ void greedy_sample_launch(long*, const void*, int, int, hipStream_t);
 void sample_launch(long*, const void*, const float*, const int*, const float*, const float*, const long*, const long*, int, int, hipStream_t);
 void mla_decode_launch(float*, const void*, const void*, const int*, const int*, int, int, int, int, int, int, float, int*, hipStream_t);
 void paged_attn_decode_launch(void*, const void*, const void*, const void*, const int*, const int*, int, int, int, int, int, float, long, int, const float*, int, float, int*, hipStream_t);
+void paged_attn_decode_fused_launch(void*, const void*, const void*, const void*, void*, void*, const long*, const float*, const long*, const int*, const int*, int, int, int, int, int, float, long, long, long, int*, hipStream_t);
 void flash_prefill_launch(void*, const void*, const void*, const void*, const int*, const int*, const int*, int, int, int, int, int, float, long, long, long, const float*, int, float, int*, hipStream_t);
 void flash_prefill_paged_launch(void*, const void*, const void*, const void*, const int*, const int*, const int*, const int*, const int*, const int*, int, int, int, int, int, float, long, const float*, int, float, int*, hipStream_t);
 void mfma_probe_launch(float*, const void*, const void*, hipStream_t);
@@ -232,6 +233,63 @@ void paged_attn_decode(at::Tensor out, at::Tensor q, at::Tensor k_cache,
                            (int)window, (float)softcap, &err, cur_stream(q));
   TORCH_CHECK(!err, "paged_attn_decode: unsupported head_dim/GQ combination: D=",
               D, " Hq=", Hq, " Hkv=", Hkv);
+  HIP_CHECK_LAST();
+}
+
+// Plain decode step in one launch: NeoX rope on q and the new k, K/V written
+// to slot_mapping, paged attention over the result. q/k/v are the unroped
+// views of the qkv buffer and stay untouched. Allocates nothing, never syncs.
+// Pays at GQ 1, 2 and 4; at GQ 5-8 the three separate ops are as fast or
+// faster (profiles/decode_fused.md) and callers should keep them.
+// Contract (the engine's decode step; not checkable without a sync): row i's
+// new token is position seq_lens[i]-1 of its sequence, and slot_mapping[i] is
+// that position's slot in block_tables[i], or < 0 for "do not write".
+void paged_attn_decode_fused(at::Tensor out, at::Tensor q, at::Tensor k,
+                             at::Tensor v, at::Tensor k_cache,
+                             at::Tensor v_cache, at::Tensor positions,
+                             at::Tensor cos_sin, at::Tensor slot_mapping,
+                             at::Tensor block_tables, at::Tensor seq_lens,
+                             double scale) {
+  check_bf16(out, "out");
+  const long qstride = row_stride_3d(q, "q");
+  const long kstride = row_stride_3d(k, "k");
+  const long vstride = row_stride_3d(v, "v");
+  check_bf16(k_cache, "k_cache"); check_bf16(v_cache, "v_cache");
+  const int N = q.size(0), Hq = q.size(1), D = q.size(2);
+  const int Hkv = k_cache.size(1);
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 16
+                  && k_cache.size(3) == D && v_cache.sizes() == k_cache.sizes(),
+              "fused decode assumes [blocks, Hkv, 16, D] pools");
+  TORCH_CHECK(out.size(0) == N && out.size(1) == Hq && out.size(2) == D);
+  TORCH_CHECK(k.size(0) == N && k.size(1) == Hkv && k.size(2) == D
+                  && v.sizes() == k.sizes() && Hq % Hkv == 0,
+              "k/v must be [N, Hkv, D] rows of the same step");
+  check_row_param(positions, at::kLong, N, "positions");
+  check_row_param(slot_mapping, at::kLong, N, "slot_mapping");
+  check_row_param(seq_lens, at::kInt, N, "seq_lens");
+  TORCH_CHECK(block_tables.is_cuda() && block_tables.scalar_type() == at::kInt
+                  && block_tables.is_contiguous() && block_tables.dim() == 2
+                  && block_tables.size(0) == N,
+              "block_tables must be contiguous int32 [N, max_blocks]");
+  TORCH_CHECK(cos_sin.is_cuda() && cos_sin.scalar_type() == at::kFloat
+                  && cos_sin.is_contiguous() && cos_sin.dim() == 2
+                  && cos_sin.size(1) == D,
+              "fused decode needs full rotary: cos_sin must be f32 [max_pos, D]");
+  // 16 B vector loads of the q/k/v rows
+  TORCH_CHECK(qstride % 8 == 0 && kstride % 8 == 0 && vstride % 8 == 0
+                  && q.storage_offset() % 8 == 0 && k.storage_offset() % 8 == 0
+                  && v.storage_offset() % 8 == 0,
+              "q/k/v rows must be 16-byte aligned");
+  int err = 0;
+  paged_attn_decode_fused_launch(
+      out.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+      k_cache.data_ptr(), v_cache.data_ptr(), positions.data_ptr<long>(),
+      cos_sin.data_ptr<float>(), slot_mapping.data_ptr<long>(),
+      block_tables.data_ptr<int>(), seq_lens.data_ptr<int>(), N, Hq, Hkv, D,
+      (int)block_tables.size(1), (float)scale, qstride, kstride, vstride, &err,
+      cur_stream(q));
+  TORCH_CHECK(!err, "paged_attn_decode_fused: unsupported head_dim/GQ "
+              "combination: D=", D, " Hq=", Hq, " Hkv=", Hkv);
   HIP_CHECK_LAST();
 }
 
@@ -533,6 +591,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_tables"), py::arg("seq_lens"), py::arg("scale"),
         py::arg("sinks") = py::none(), py::arg("window") = 0,
         py::arg("softcap") = 0.0);
+  m.def("paged_attn_decode_fused", &paged_attn_decode_fused,
+        "neox rope + KV-cache write + paged GQA decode attention, one launch",
+        py::arg("out"), py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"),
+        py::arg("cos_sin"), py::arg("slot_mapping"), py::arg("block_tables"),
+        py::arg("seq_lens"), py::arg("scale"));
   m.def("flash_prefill", &flash_prefill, "varlen causal MFMA prefill attention",
         py::arg("out"), py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("tile_start"), py::arg("tile_q0"), py::arg("tile_len"),

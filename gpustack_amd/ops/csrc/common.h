@@ -90,6 +90,30 @@ __device__ __forceinline__ float group16_reduce_sum(float x) {
   return x;
 }
 
+// DPP lane selects inside a 16-lane row: VALU operand modifiers, no LDS
+// crossbar traffic (__shfl_xor compiles to ds_bpermute_b32).
+template <int CTRL>
+__device__ __forceinline__ unsigned int dpp_mov(unsigned int x) {
+  return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf,
+                                                   false);
+}
+// lane i reads the dword N lanes round its row (row_ror:N); N=8 is lane i^8
+template <int N>
+__device__ __forceinline__ unsigned int dpp_row_ror(unsigned int x) {
+  static_assert(N >= 1 && N <= 15, "row_ror takes 1..15");
+  return dpp_mov<0x120 + N>(x);
+}
+// lane i reads lane i^M of its row, M in {1, 2, 4, 8}
+template <int M>
+__device__ __forceinline__ unsigned int dpp_row_xor(unsigned int x) {
+  static_assert(M == 1 || M == 2 || M == 4 || M == 8, "xor mask");
+  if constexpr (M == 8) return dpp_mov<0x128>(x);        // row_ror:8
+  else if constexpr (M == 4)                             // i^7, then ^3
+    return dpp_mov<0x1B>(dpp_mov<0x141>(x));  // row_half_mirror, quad [3,2,1,0]
+  else if constexpr (M == 2) return dpp_mov<0x4E>(x);    // quad_perm [2,3,0,1]
+  else return dpp_mov<0xB1>(x);                          // quad_perm [1,0,3,2]
+}
+
 #define HIP_CHECK_KERNEL()                                        \
   do {                                                            \
     hipError_t e_ = hipGetLastError();                            \
