@@ -501,4 +501,69 @@ def fp8_linear(x, qw, ws, bias=None):
     return out
 
 
+# --- multi-LoRA (grouped shrink/expand, csrc/lora.hip) ----------------------
+
+LORA_TILE_ROWS = 16
+
+
+def lora_kernel_enabled() -> bool:
+    """GPUSTACK_AMD_LORA_KERNEL=0 keeps multi-LoRA on the per-adapter,
+    per-projection torch loop (models/lora.py); default on."""
+    return os.environ.get("GPUSTACK_AMD_LORA_KERNEL", "1") != "0"
+
+
+def build_lora_tiles(row_slots: list[int], device, bank_rows=None):
+    """Per-batch tile metadata for lora_apply: (row_idx int32 [Tl], tiles
+    int32 [ntiles, 3]). `bank_rows` maps an adapter slot to its row of the
+    stacked site tensors (default: the slot itself); rows of the batch whose
+    slot is 0 or not in the map are left out. row_idx lists the others
+    sorted by bank row; a tile is (bank row, first, count <= 16) over row_idx
+    and never spans two bank rows. Both are views of ONE tensor, so the
+    batch costs one host-to-device copy. None when no row qualifies."""
+    rows = sorted((s if bank_rows is None else bank_rows[s], i)
+                  for i, s in enumerate(row_slots)
+                  if s > 0 and (bank_rows is None or s in bank_rows))
+    if not rows:
+        return None
+    tiles, first = [], 0
+    while first < len(rows):
+        brow, n = rows[first][0], 1
+        while (n < LORA_TILE_ROWS and first + n < len(rows)
+               and rows[first + n][0] == brow):
+            n += 1
+        tiles += [brow, first, n]
+        first += n
+    buf = torch.tensor([i for _, i in rows] + tiles, dtype=torch.int32,
+                       device=device)
+    return buf[:len(rows)], buf[len(rows):].view(-1, 3)
+
+
+def lora_ksplit(ntiles: int, K: int) -> int:
+    """K splits of the shrink grid: enough blocks to cover the 256 CUs while
+    a block keeps at least 16 MFMA k-steps (4 per wave), at most 8 ways."""
+    return max(1, min(8, K // 512, 256 // max(1, ntiles)))
+
+
+def lora_apply(out, x, A_site, B_site, seg_starts, row_idx, tiles,
+               ksplit: int | None = None) -> None:
+    """out[row, j] += (x[row] @ A_site[slot]^T)[p(j)*R:(p(j)+1)*R]
+    @ B_site[slot, j] for every row listed in row_idx, slot (the row of the
+    site tensors) taken from the row's tile (build_lora_tiles). A_site [S, P*R, K] and B_site [S, N, R]
+    stack a call site's P projections; seg_starts are their first output
+    columns. Rows outside row_idx are not touched. The HIP path needs bf16,
+    contiguous x/out, K%64==0, segment starts and sizes %16==0, R in
+    {16, 32, 64}, and raises otherwise."""
+    hip = _backend(x)
+    if hip is None:
+        torch_ref.lora_apply(out, x, A_site, B_site, seg_starts, row_idx,
+                             tiles)
+        return
+    if ksplit is None:
+        ksplit = lora_ksplit(tiles.shape[0], x.shape[1])
+    ws = _splitk_workspace(ksplit * row_idx.numel() * A_site.shape[1],
+                           x.device)
+    hip.lora_apply(out, x, A_site, B_site, list(seg_starts), row_idx, tiles,
+                   ws, ksplit)
+
+
 build_cos_sin_cache = torch_ref.build_cos_sin_cache

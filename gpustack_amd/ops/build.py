@@ -18,8 +18,15 @@ CSRC = PKG_DIR / "csrc"
 SO_PATH = PKG_DIR / "_hip_ops.so"
 ARCH = os.environ.get("GPUSTACK_AMD_ARCH", "gfx950")
 
-HIP_SOURCES = ["pointwise.hip", "attn_decode.hip", "attn_prefill.hip", "skinny_gemm.hip", "gemm8.hip", "gemm8_lab.hip", "moe_gemm.hip", "w4_gemm.hip", "fp8_gemm.hip", "mla_decode.hip", "sample.hip"]
+HIP_SOURCES = ["pointwise.hip", "attn_decode.hip", "attn_prefill.hip", "skinny_gemm.hip", "gemm8.hip", "gemm8_lab.hip", "moe_gemm.hip", "w4_gemm.hip", "fp8_gemm.hip", "mla_decode.hip", "sample.hip", "lora.hip"]
 CPP_SOURCES = ["bindings.cpp"]
+# Per-source flags. lora.hip is built with the packed-f32 VALU ops
+# (v_pk_add/mul/fma_f32) turned off: the kernels' f32 reductions and the f32
+# add into `out` then use the one-result ops the kernels were validated
+# with on the MI355X. It is not a speed choice: neither build uses scratch,
+# and the occupancies of docs/KERNELS.md are the same either way.
+EXTRA_FLAGS = {"lora.hip": ["-Xclang", "-target-feature", "-Xclang",
+                            "-packed-fp32-ops"]}
 
 
 def _torch_paths():
@@ -91,7 +98,8 @@ def build(verbose: bool = False, force: bool = False) -> Path:
         ):
             objs.append(str(obj))
             continue
-        cmd = ["hipcc", *flags, *inc_flags, "-c", str(srcp), "-o", str(obj)]
+        cmd = ["hipcc", *flags, *EXTRA_FLAGS.get(src, []), *inc_flags, "-c",
+               str(srcp), "-o", str(obj)]
         if src.endswith(".cpp"):
             cmd.insert(1, "-x")
             cmd.insert(2, "hip")  # binding file still needs hip runtime types

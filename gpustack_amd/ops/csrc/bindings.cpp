@@ -31,6 +31,7 @@ void fp8_quant_rows_launch(void*, void*, const void*, int, int, int*, hipStream_
 void fp8_dequant_launch(void*, const void*, long, hipStream_t);
 void fp8_scale_out_launch(void*, const void*, const void*, long, int, int*, hipStream_t);
 void fp8_mfma_probe_launch(float*, const void*, const void*, hipStream_t);
+void lora_apply_launch(void*, const void*, const void*, const void*, float*, const int*, const int*, int, int, int, int, int, int, int, int, int, int, int, int*, hipStream_t);
 
 #define HIP_CHECK_LAST()                                                     \
   do {                                                                       \
@@ -552,6 +553,45 @@ at::Tensor fp8_mfma_probe(at::Tensor a, at::Tensor b) {
   return d;
 }
 
+// out[row_idx] += lora delta of the tile's slot (lora.hip). seg_starts: first
+// output column of each of the site's P projections.
+void lora_apply(at::Tensor out, at::Tensor x, at::Tensor a_site,
+                at::Tensor b_site, std::vector<long> seg_starts,
+                at::Tensor row_idx, at::Tensor tiles, at::Tensor workspace,
+                long ksplit) {
+  check_bf16(out, "out"); check_bf16(x, "x");
+  check_bf16(a_site, "A_site"); check_bf16(b_site, "B_site");
+  check_f32(workspace, "workspace");
+  for (auto* t : {&row_idx, &tiles}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt &&
+                t->is_contiguous(), "row_idx/tiles must be int32 on GPU");
+  }
+  TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && a_site.dim() == 3 &&
+              b_site.dim() == 3 && tiles.numel() % 3 == 0);
+  const int T = x.size(0), K = x.size(1), N = out.size(1);
+  const int S = a_site.size(0), R = b_site.size(2);
+  const int P = (int)seg_starts.size();
+  const int Tl = row_idx.numel(), ntiles = tiles.numel() / 3;
+  TORCH_CHECK(out.size(0) == T && b_site.size(0) == S && b_site.size(1) == N &&
+              a_site.size(2) == K && a_site.size(1) == (long)P * R,
+              "lora_apply: bank/site shapes disagree");
+  TORCH_CHECK(P >= 1 && P <= 3 && seg_starts[0] == 0, "1..3 segments from 0");
+  for (int p = 1; p < P; ++p)
+    TORCH_CHECK(seg_starts[p] > seg_starts[p - 1] && seg_starts[p] < N);
+  TORCH_CHECK(Tl <= T && ntiles <= Tl && ksplit >= 1 &&
+              workspace.numel() >= ksplit * Tl * P * R, "workspace too small");
+  int err = 0;
+  lora_apply_launch(out.data_ptr(), x.data_ptr(), a_site.data_ptr(),
+                    b_site.data_ptr(), workspace.data_ptr<float>(),
+                    row_idx.data_ptr<int>(), tiles.data_ptr<int>(), ntiles, Tl,
+                    T, S, K, N, P, R, P > 1 ? (int)seg_starts[1] : N,
+                    P > 2 ? (int)seg_starts[2] : N, (int)ksplit, &err,
+                    cur_stream(x));
+  TORCH_CHECK(!err, "lora_apply: unsupported shape K=", K, " N=", N, " R=", R,
+              " (need K%64==0, segments %16==0, R in {16,32,64})");
+  HIP_CHECK_LAST();
+}
+
 void gemm_lab(at::Tensor out, at::Tensor x, at::Tensor w, long mode) {
   check_bf16(out, "out"); check_bf16(x, "x"); check_bf16(w, "w");
   const int M = x.size(0), K = x.size(1), N = w.size(0);
@@ -634,6 +674,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fp8_dequant", &fp8_dequant, "exact e4m3 -> bf16 up-conversion");
   m.def("fp8_scale_out", &fp8_scale_out,
         "in-place out[m,n] *= xs[m]*ws[n] (W8A8 fallback epilogue)");
+  m.def("lora_apply", &lora_apply,
+        "grouped multi-LoRA shrink + expand-add over slot-sorted row tiles");
   m.def("fp8_mfma_probe", &fp8_mfma_probe,
         "16x16x32 fp8 MFMA layout probe");
 }

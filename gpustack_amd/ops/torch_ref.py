@@ -470,3 +470,20 @@ def fp8_linear(x: torch.Tensor, qw: torch.Tensor, ws: torch.Tensor,
     if bias is not None:
         out += bias
     return out
+
+
+def lora_apply(out: torch.Tensor, x: torch.Tensor, A_site: torch.Tensor,
+               B_site: torch.Tensor, seg_starts, row_idx: torch.Tensor,
+               tiles: torch.Tensor) -> None:
+    """Grouped multi-LoRA (contract: ops.lora_apply): h = x @ A^T in fp32,
+    rounded to the serving dtype once, then each projection's segment of h
+    times its B rows, added to `out` in fp32 and rounded once."""
+    R, N = B_site.shape[2], out.shape[1]
+    ends = list(seg_starts[1:]) + [N]
+    idx = row_idx.long()
+    for slot, first, count in tiles.tolist():
+        rows = idx[first:first + count]
+        h = (x[rows].float() @ A_site[slot].float().t()).to(x.dtype).float()
+        for p, (s, e) in enumerate(zip(seg_starts, ends)):
+            d = h[:, p * R:(p + 1) * R] @ B_site[slot, s:e].float().t()
+            out[rows, s:e] = (out[rows, s:e].float() + d).to(out.dtype)
