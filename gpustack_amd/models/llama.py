@@ -704,6 +704,28 @@ class MoEMLP(nn.Module):
         logits = F.linear(x.float(), rw)                          # [T, E]
         if self.spec.router_logit_bias and self.router_bias is not None:
             logits = logits + self.router_bias  # GPT-OSS: bias on logits
+        # The dispatch path is decided before routing, from T, k, E,
+        # _fused_ok and capture alone (the three paths are described below).
+        # On the fused path the routing itself is two HIP launches
+        # (ops/csrc/moe_route.hip) instead of the torch chain that follows.
+        capturing = x.is_cuda and torch.cuda.is_current_stream_capturing()
+        fused = self._fused_ok(x) and (T * self.top_k <= 32 * self.e
+                                       or capturing)
+        sigmoid = self.spec.router_mode == "sigmoid_bias"
+        ng = self.spec.n_group if sigmoid else 1
+        if (fused and ops.moe_route_kernel_enabled()
+                and ops.moe_route_supported(self.e, self.top_k, ng)):
+            experts, weights = ops.moe_route(
+                logits, self.top_k,
+                mode="sigmoid_bias" if sigmoid else "softmax",
+                renorm=self.spec.norm_topk_prob,
+                bias=self.router_bias if sigmoid else None, n_group=ng,
+                topk_group=self.spec.topk_group if sigmoid else 1,
+                scale=self.spec.routed_scaling_factor if sigmoid else 1.0)
+            s_tok, order, offs, counts = ops.moe_align(experts, self.e)
+            out = self._expert_gemms(x, s_tok, order, offs, counts,
+                                     weights.reshape(-1))
+            return self.comm.all_reduce(self._add_shared(x, out))
         if self.spec.router_mode == "sigmoid_bias":
             # GLM-4.5/DeepSeek routing (HF Glm4MoeTopkRouter): sigmoid
             # scores; the learned bias only influences the CHOICE, the
@@ -755,9 +777,7 @@ class MoEMLP(nn.Module):
         # fused path is forced for ANY size: the torch fallbacks sync with
         # the host per layer, which capture cannot record (large decode
         # buckets on many-expert models would otherwise crash at init).
-        capturing = x.is_cuda and torch.cuda.is_current_stream_capturing()
-        if self._fused_ok(x) and (flat_exp.numel() <= 32 * self.e
-                                  or capturing):
+        if fused:
             out = self._fused_dispatch(x, flat_exp, flat_tok, flat_w32,
                                        ones_i32)
             return self.comm.all_reduce(self._add_shared(x, out))
@@ -872,14 +892,20 @@ class MoEMLP(nn.Module):
         tensor shape here depends only on (T, k, E) — safe under hipGraph
         capture (reference capability: vLLM fused_moe; re-designed for
         CDNA4 per SURVEY.md §2.9 #1)."""
-        T = x.shape[0]
-        TK = flat_exp.numel()
         order = torch.argsort(flat_exp, stable=True)
         s_tok = flat_tok[order].to(torch.int32)
         # scatter_add instead of bincount: bincount computes max() on host
         counts = torch.zeros(self.e, dtype=torch.int32, device=x.device)
         counts.scatter_add_(0, flat_exp, ones_i32)
         offs = (counts.cumsum(0, dtype=torch.int32) - counts).to(torch.int32)
+        return self._expert_gemms(x, s_tok, order.to(torch.int32), offs,
+                                  counts, flat_w32)
+
+    def _expert_gemms(self, x, s_tok, order, offs, counts, flat_w32):
+        """The two grouped expert GEMMs over the expert-sorted assignment
+        list (all index tensors int32) and the sum over the k axis."""
+        T = x.shape[0]
+        TK = order.numel()
         hip = ops._load_hip()
         act = x.new_empty(TK, self.i)
         act_mode = 1 if self.spec.moe_act == "clamped_swiglu" else 0
@@ -889,7 +915,7 @@ class MoEMLP(nn.Module):
         # down bias on tp rank 0 only: the TP all-reduce must sum it once
         db = self.down_b if self.comm.tp_rank == 0 else None
         hip.moe_down_scale(contrib, act, self._bank("down"), offs, counts,
-                           order.to(torch.int32), flat_w32, bias=db)
+                           order, flat_w32, bias=db)
         return contrib.view(T, self.top_k, -1).sum(dim=1).to(x.dtype)
 
     def _act_mul(self, gu):

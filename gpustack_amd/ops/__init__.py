@@ -566,4 +566,53 @@ def lora_apply(out, x, A_site, B_site, seg_starts, row_idx, tiles,
                    ws, ksplit)
 
 
+# --- MoE routing (top-k gating + expert sort, csrc/moe_route.hip) -----------
+
+def moe_route_kernel_enabled() -> bool:
+    """GPUSTACK_AMD_MOE_ROUTE_KERNEL=0 keeps MoE routing on the torch chain
+    of models/llama.py MoEMLP; default on."""
+    return os.environ.get("GPUSTACK_AMD_MOE_ROUTE_KERNEL", "1") != "0"
+
+
+def moe_route_supported(E: int, top_k: int, n_group: int = 1) -> bool:
+    """Shapes the HIP routing kernels take: E <= 512, k <= min(16, E) and,
+    with grouped routing, groups of 2..64 experts whose size divides 64."""
+    if not (1 <= top_k <= min(16, E) and E <= 512 and n_group >= 1
+            and E % n_group == 0):
+        return False
+    gsz = E // n_group
+    return n_group == 1 or (2 <= gsz <= 64 and 64 % gsz == 0)
+
+
+def moe_route(logits, top_k: int, *, mode: str, renorm: bool, bias=None,
+              n_group: int = 1, topk_group: int = 1, scale: float = 1.0):
+    """Top-k gating of router logits [T, E] f32 -> (experts [T, k] int32,
+    weights [T, k] f32). mode "softmax": top-k of the logits, weights their
+    softmax (renorm) or their full-softmax probabilities. mode
+    "sigmoid_bias": choice = sigmoid(logits) + bias, optionally restricted to
+    the topk_group groups with the largest top-2 choice sum, weights the
+    sigmoid scores, / (sum + 1e-20) if renorm, * scale. Larger value first,
+    lower index on ties. The HIP path raises outside moe_route_supported."""
+    if mode not in ("softmax", "sigmoid_bias"):
+        raise ValueError(f"unknown router mode {mode!r}")
+    hip = _backend(logits)
+    if hip is None:
+        return torch_ref.moe_route(logits, top_k, mode=mode, renorm=renorm,
+                                   bias=bias, n_group=n_group,
+                                   topk_group=topk_group, scale=scale)
+    return hip.moe_route(logits, top_k, mode == "sigmoid_bias", bool(renorm),
+                         bias, n_group, topk_group, float(scale))
+
+
+def moe_align(experts, E: int):
+    """experts [T, k] int32 -> (s_tok, order [T*k], offs, counts [E]), int32:
+    order = stable argsort of the flat list, s_tok = order // k, counts per
+    expert and their exclusive prefix sum (what moe_gate_up_silu and
+    moe_down_scale consume)."""
+    hip = _backend(experts)
+    if hip is None:
+        return torch_ref.moe_align(experts, E)
+    return hip.moe_align(experts, E)
+
+
 build_cos_sin_cache = torch_ref.build_cos_sin_cache

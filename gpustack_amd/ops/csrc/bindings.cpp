@@ -32,6 +32,8 @@ void fp8_dequant_launch(void*, const void*, long, hipStream_t);
 void fp8_scale_out_launch(void*, const void*, const void*, long, int, int*, hipStream_t);
 void fp8_mfma_probe_launch(float*, const void*, const void*, hipStream_t);
 void lora_apply_launch(void*, const void*, const void*, const void*, float*, const int*, const int*, int, int, int, int, int, int, int, int, int, int, int, int*, hipStream_t);
+void moe_route_launch(int*, float*, const float*, const float*, int, int, int, int, int, int, int, float, int*, hipStream_t);
+void moe_align_launch(int*, int*, int*, int*, const int*, int, int, int, hipStream_t);
 
 #define HIP_CHECK_LAST()                                                     \
   do {                                                                       \
@@ -592,6 +594,58 @@ void lora_apply(at::Tensor out, at::Tensor x, at::Tensor a_site,
   HIP_CHECK_LAST();
 }
 
+// Router logits [T, E] f32 -> (experts [T, k] i32, weights [T, k] f32)
+// (moe_route.hip). sigmoid: GLM/DeepSeek sigmoid + choice bias (+ groups).
+std::tuple<at::Tensor, at::Tensor> moe_route(
+    at::Tensor logits, long top_k, bool sigmoid, bool renorm,
+    c10::optional<at::Tensor> bias, long n_group, long topk_group,
+    double scale) {
+  check_f32(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 &&
+              logits.size(0) * top_k < INT_MAX, "logits must be [T >= 1, E]");
+  const int T = logits.size(0), E = logits.size(1);
+  const float* bias_ptr = nullptr;
+  if (bias.has_value()) {
+    check_f32(*bias, "bias");
+    TORCH_CHECK(sigmoid && bias->numel() == E,
+                "bias is the sigmoid router's, one value per expert");
+    bias_ptr = bias->data_ptr<float>();
+  }
+  auto experts = at::empty({T, top_k}, logits.options().dtype(at::kInt));
+  auto weights = at::empty({T, top_k}, logits.options());
+  int err = 0;
+  moe_route_launch(experts.data_ptr<int>(), weights.data_ptr<float>(),
+                   logits.data_ptr<float>(), bias_ptr, T, E, (int)top_k,
+                   sigmoid, renorm, (int)n_group, (int)topk_group,
+                   (float)scale, &err, cur_stream(logits));
+  TORCH_CHECK(!err, "moe_route: unsupported shape E=", E, " k=", top_k,
+              " n_group=", n_group, " topk_group=", topk_group,
+              " (need E <= 512, k <= min(16, E), groups of 2..64 experts "
+              "that divide 64, sigmoid router only)");
+  HIP_CHECK_LAST();
+  return {experts, weights};
+}
+
+// experts [T, k] i32 in [0, E) -> (s_tok, order [T*k], offs, counts [E]):
+// the stable sort by expert that the grouped GEMMs consume (moe_route.hip).
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> moe_align(
+    at::Tensor experts, long E) {
+  TORCH_CHECK(experts.is_cuda() && experts.scalar_type() == at::kInt &&
+              experts.is_contiguous() && experts.dim() == 2,
+              "experts must be a contiguous [T, k] int32 GPU tensor");
+  TORCH_CHECK(E >= 1 && E <= 65535 && experts.numel() >= 1);
+  const int n = experts.numel(), k = experts.size(1);
+  auto s_tok = at::empty({n}, experts.options());
+  auto order = at::empty({n}, experts.options());
+  auto offs = at::empty({E}, experts.options());
+  auto counts = at::empty({E}, experts.options());
+  moe_align_launch(s_tok.data_ptr<int>(), order.data_ptr<int>(),
+                   offs.data_ptr<int>(), counts.data_ptr<int>(),
+                   experts.data_ptr<int>(), n, k, (int)E, cur_stream(experts));
+  HIP_CHECK_LAST();
+  return {s_tok, order, offs, counts};
+}
+
 void gemm_lab(at::Tensor out, at::Tensor x, at::Tensor w, long mode) {
   check_bf16(out, "out"); check_bf16(x, "x"); check_bf16(w, "w");
   const int M = x.size(0), K = x.size(1), N = w.size(0);
@@ -663,6 +717,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("counts"), py::arg("order"), py::arg("flat_w"),
         py::arg("bias") = py::none(),
         "grouped MoE down GEMM + routing-weight scale/scatter");
+  m.def("moe_route", &moe_route,
+        py::arg("logits"), py::arg("top_k"), py::arg("sigmoid"),
+        py::arg("renorm"), py::arg("bias") = py::none(),
+        py::arg("n_group") = 1, py::arg("topk_group") = 1,
+        py::arg("scale") = 1.0,
+        "fused MoE top-k gating: softmax / sigmoid+bias / grouped routers");
+  m.def("moe_align", &moe_align, py::arg("experts"), py::arg("E"),
+        "stable sort of the assignment list by expert, offsets and counts");
   m.def("w4_gemm", &w4_gemm,
         "W4A16 GEMM: packed-int4 weights dequantized in-register");
   m.def("w4_dequant", &w4_dequant,

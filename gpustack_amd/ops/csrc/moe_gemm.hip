@@ -3,8 +3,9 @@
 // padded-bmm overcompute so MoE decode can run under hipGraphs).
 //
 // Two kernels over the expert-sorted assignment list (sorting/count/offset
-// tensors are computed on-device by torch ops in models/llama.py MoEMLP —
-// no host readback anywhere):
+// tensors are computed on-device by moe_align in moe_route.hip, or by torch
+// ops in models/llama.py MoEMLP where that kernel is switched off or out of
+// range — no host readback anywhere):
 //
 //   moe_gate_up_silu: act[j, :] = silu(x[tok_j] @ Wg[e_j]^T) * (x[tok_j] @ Wu[e_j]^T)
 //   moe_down_scale:   contrib[order[j], :] = (act[j] @ Wd[e_j]^T) * w_j

@@ -487,3 +487,50 @@ def lora_apply(out: torch.Tensor, x: torch.Tensor, A_site: torch.Tensor,
         for p, (s, e) in enumerate(zip(seg_starts, ends)):
             d = h[:, p * R:(p + 1) * R] @ B_site[slot, s:e].float().t()
             out[rows, s:e] = (out[rows, s:e].float() + d).to(out.dtype)
+
+
+def moe_route(logits: torch.Tensor, top_k: int, *, mode: str, renorm: bool,
+              bias: torch.Tensor | None = None, n_group: int = 1,
+              topk_group: int = 1, scale: float = 1.0):
+    """MoE top-k gating (contract: ops.moe_route), f32. Larger value first,
+    lower index on equal values, for experts and for groups: a stable
+    descending sort. Returns (experts [T, k] int32, weights [T, k] f32)."""
+    T, E = logits.shape
+    logits = logits.float()
+    if mode == "softmax":
+        order = torch.sort(logits, dim=-1, descending=True, stable=True)[1]
+        experts = order[:, :top_k]
+        if renorm:
+            weights = torch.softmax(logits.gather(1, experts), dim=-1)
+        else:
+            weights = torch.softmax(logits, dim=-1).gather(1, experts)
+        return experts.to(torch.int32), weights
+    if mode != "sigmoid_bias":
+        raise ValueError(f"unknown router mode {mode!r}")
+    scores = torch.sigmoid(logits)
+    choice = scores if bias is None else scores + bias.float()
+    if n_group > 1:
+        gs = choice.view(T, n_group, E // n_group).topk(2, dim=-1)[0].sum(-1)
+        gi = torch.sort(gs, dim=-1, descending=True, stable=True)[1]
+        keep = torch.zeros_like(gs, dtype=torch.bool)
+        keep.scatter_(1, gi[:, :topk_group], True)
+        choice = choice.masked_fill(
+            ~keep.repeat_interleave(E // n_group, dim=1), float("-inf"))
+    order = torch.sort(choice, dim=-1, descending=True, stable=True)[1]
+    experts = order[:, :top_k]
+    weights = scores.gather(1, experts)
+    if renorm:
+        weights = weights / (weights.sum(dim=-1, keepdim=True) + 1e-20)
+    return experts.to(torch.int32), weights * scale
+
+
+def moe_align(experts: torch.Tensor, E: int):
+    """Stable sort of the flat assignment list by expert (contract:
+    ops.moe_align): (s_tok, order [T*k], offs, counts [E]), all int32."""
+    flat = experts.reshape(-1).long()
+    order = torch.argsort(flat, stable=True)
+    counts = torch.bincount(flat, minlength=E)
+    offs = counts.cumsum(0) - counts
+    return ((order // experts.shape[1]).to(torch.int32),
+            order.to(torch.int32), offs.to(torch.int32),
+            counts.to(torch.int32))
