@@ -636,6 +636,11 @@ class EngineConfig:
     # channel, activations are quantized per token at each use
     # (ops/csrc/fp8_gemm.hip). lm_head, embeddings, MLA projections and
     # MoE expert banks stay bf16; not combinable with cpu_offload_gb yet
+    # FP8 runtime with expert banks ("fp8_moe"): everything "fp8" does, and
+    # the expert banks of eligible MoE layers (silu, no expert biases,
+    # I_local%128 == 0, H%128 == 0) are held as e4m3 with one f32 scale per
+    # expert output row and read by the grouped W8A8 expert GEMMs
+    # (ops/csrc/moe_gemm_fp8.hip); router and shared experts stay bf16
     quantize_runtime: str | None = None
     # CPU weight offload (reference: vLLM --cpu-offload-gb, the GGUF
     # partial-offload placement): ~this many GiB of trailing layers'

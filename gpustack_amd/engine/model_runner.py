@@ -331,18 +331,23 @@ class ModelRunner:
 
             logging.getLogger(__name__).info(
                 "W4 runtime: %d weight tensors packed int4", n)
-        if getattr(cfg, "quantize_runtime", None) == "fp8":
+        if getattr(cfg, "quantize_runtime", None) in ("fp8", "fp8_moe"):
             if getattr(cfg, "cpu_offload_gb", 0) > 0:
                 raise ValueError(
-                    "quantize_runtime='fp8' with cpu_offload_gb > 0 is not "
-                    "supported yet")
+                    f"quantize_runtime={cfg.quantize_runtime!r} with "
+                    "cpu_offload_gb > 0 is not supported yet")
             from ..models.weights import convert_to_fp8_runtime
 
             n = convert_to_fp8_runtime(self.model, cfg)
+            n_banks = sum(
+                getattr(layer.mlp, pname, None) is not None
+                for layer in self.model.layers
+                for pname in ("gate_up_fp8", "down_fp8"))
             import logging
 
             logging.getLogger(__name__).info(
-                "FP8 runtime: %d weight tensors packed e4m3 (W8A8)", n)
+                "FP8 runtime: %d weight tensors packed e4m3 (W8A8), "
+                "%d of them MoE expert banks", n, n_banks)
         if getattr(cfg, "cpu_offload_gb", 0) > 0:
             from .offload import setup_cpu_offload
 

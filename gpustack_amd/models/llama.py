@@ -637,6 +637,12 @@ class MoEMLP(nn.Module):
         # (resident capacity is the point: Qwen3-235B W4 fits one GPU)
         self.gate_up_packs: list | None = None
         self.down_packs: list | None = None
+        # FP8 runtime with expert banks (weights.convert_to_fp8_runtime,
+        # quantize_runtime="fp8_moe"): each bank as ONE Fp8Pack, qw e4m3
+        # [E, 2I, h] / [E, h, I], ws f32 [E, 2I] / [E, h]; the bf16
+        # parameters are freed. Both are set or neither.
+        self.gate_up_fp8: Fp8Pack | None = None
+        self.down_fp8: Fp8Pack | None = None
         # GLM/DeepSeek-style extensions (spec.router_mode "sigmoid_bias"):
         # learned correction bias on the routing scores and a SHARED dense
         # expert applied to every token (TP shards its intermediate)
@@ -796,7 +802,8 @@ class MoEMLP(nn.Module):
         # [E=128, M~800, K=2048] bf16 even with 64-aligned M; standalone
         # repros at smaller caps pass) — the per-expert loop is the safe
         # prefill path until the library issue is understood
-        use_bmm = (self.e >= 16 and x.is_cuda
+        # (FP8 banks have no bf16 bank to batch over: they take the loop)
+        use_bmm = (self.e >= 16 and x.is_cuda and self.gate_up_fp8 is None
                    and _os.environ.get("GPUSTACK_AMD_MOE_BMM", "0") == "1")
         if use_bmm:
             counts = torch.zeros(self.e, dtype=torch.long, device=x.device)
@@ -847,6 +854,9 @@ class MoEMLP(nn.Module):
 
     def _expert_w(self, which: str, e: int):
         """Per-expert weight for the loop path (qlinear handles packs)."""
+        bank = self.gate_up_fp8 if which == "gate_up" else self.down_fp8
+        if bank is not None:  # a view of the bank: no copy, no dequant
+            return None, Fp8Pack(bank.qw[e], bank.ws[e])
         packs = (self.gate_up_packs if which == "gate_up"
                  else self.down_packs)
         w = self.gate_up_w if which == "gate_up" else self.down_w
@@ -906,6 +916,18 @@ class MoEMLP(nn.Module):
         list (all index tensors int32) and the sum over the k axis."""
         T = x.shape[0]
         TK = order.numel()
+        if self.gate_up_fp8 is not None:
+            # FP8 banks (ops/csrc/moe_gemm_fp8.hip): x is quantized once per
+            # layer before the gather, act once between the two GEMMs; the
+            # banks are read as codes, never dequantized into _bank_scratch
+            gp, dp = self.gate_up_fp8, self.down_fp8
+            xq, xs = ops.fp8_quant_rows(x.contiguous())
+            act = ops.moe_gate_up_silu_fp8(xq, xs, gp.qw, gp.ws, s_tok, offs,
+                                           counts)
+            aq, as_ = ops.fp8_quant_rows(act)
+            contrib = ops.moe_down_scale_fp8(aq, as_, dp.qw, dp.ws, offs,
+                                             counts, order, flat_w32)
+            return contrib.view(T, self.top_k, -1).sum(dim=1).to(x.dtype)
         hip = ops._load_hip()
         act = x.new_empty(TK, self.i)
         act_mode = 1 if self.spec.moe_act == "clamped_swiglu" else 0

@@ -751,12 +751,32 @@ def convert_to_fp8_runtime(model, cfg: EngineConfig) -> int:
     Stays bf16:
       - lm_head and the embeddings (the sampler reads these logits);
       - MLA attention projections (no qlinear dispatch there);
-      - MoE expert banks (the fused MoE kernels read bf16 banks).
+      - the MoE router and shared experts;
+      - MoE expert banks under quantize_runtime="fp8" (the bf16 fused MoE
+        kernels read bf16 banks).
+
+    quantize_runtime="fp8_moe" also packs the expert banks of every
+    eligible MoE layer (silu, no expert biases, I_local%128 == 0 and
+    H%128 == 0) for ops/csrc/moe_gemm_fp8.hip: each bank becomes one e4m3
+    tensor of its own shape with one f32 scale per expert output row
+    ([E, 2I] and [E, H]), each expert quantized by the same definition.
+    Ineligible layers (GPT-OSS, unaligned dims) keep their bf16 banks.
     """
     from ..ops import quantize_fp8_weight
     from .llama import Fp8Pack
 
     n_packed = 0
+
+    def pack_bank(mlp, wname: str, pname: str) -> None:
+        nonlocal n_packed
+        w = getattr(mlp, wname)
+        qw = torch.empty(w.shape, dtype=torch.float8_e4m3fn, device=w.device)
+        ws = torch.empty(w.shape[:2], dtype=torch.float32, device=w.device)
+        for e in range(w.shape[0]):  # per expert: bounds the f32 transient
+            qw[e], ws[e] = quantize_fp8_weight(w.data[e])
+        setattr(mlp, pname, Fp8Pack(qw, ws))
+        w.data = torch.empty(0, dtype=w.dtype, device=w.device)
+        n_packed += 1
 
     def pack_site(mod, wname: str, pname: str) -> None:
         nonlocal n_packed
@@ -777,6 +797,14 @@ def convert_to_fp8_runtime(model, cfg: EngineConfig) -> int:
         if not hasattr(layer.mlp, "router_w"):
             pack_site(layer.mlp, "gate_up_w", "gate_up_pack")
             pack_site(layer.mlp, "down_w", "down_pack")
+        elif (cfg.quantize_runtime == "fp8_moe"
+              and model.spec.moe_act == "silu"
+              and layer.mlp.gate_up_b is None
+              and layer.mlp.gate_up_w.numel() > 0
+              and layer.mlp.i % 128 == 0
+              and model.spec.hidden_size % 128 == 0):
+            pack_bank(layer.mlp, "gate_up_w", "gate_up_fp8")
+            pack_bank(layer.mlp, "down_w", "down_fp8")
     if model.device.type == "cuda":
         torch.cuda.empty_cache()
     return n_packed

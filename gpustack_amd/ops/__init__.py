@@ -615,4 +615,41 @@ def moe_align(experts, E: int):
     return hip.moe_align(experts, E)
 
 
+# --- FP8 expert banks (grouped W8A8 expert GEMMs, csrc/moe_gemm_fp8.hip) ----
+
+def moe_gate_up_silu_fp8(xq, xs, wq, ws, s_tok, offs, counts):
+    """act [TK, I] bf16 over the expert-sorted assignment list of moe_align:
+    act[j] = silu(g) * u, g = (xq[s_tok[j]] @ wq[e_j, :I]^T) * xs[s_tok[j]]
+    * ws[e_j, :I], u the same with the up half. xq [T, H] e4m3 and xs [T]
+    come from fp8_quant_rows; wq [E, 2I, H] e4m3, ws [E, 2I] f32. The HIP
+    path needs H%128==0 and I%128==0 and raises otherwise."""
+    act = torch.empty(s_tok.numel(), wq.shape[1] // 2, dtype=torch.bfloat16,
+                      device=xq.device)
+    hip = _backend(xq)
+    if hip is None:
+        torch_ref.moe_gate_up_silu_fp8(act, xq, xs, wq, ws, s_tok, offs,
+                                       counts)
+    else:
+        hip.moe_gate_up_silu_fp8(act, xq, xs, wq, ws, s_tok, offs, counts)
+    return act
+
+
+def moe_down_scale_fp8(aq, as_, wq, ws, offs, counts, order, flat_w):
+    """contrib [TK, H] bf16 in the original assignment order:
+    contrib[order[j]] = (aq[j] @ wq[e_j]^T) * as_[j] * ws[e_j]
+    * flat_w[order[j]]. aq [TK, I] e4m3 and as_ [TK] are the quantized rows
+    of act (sorted order); wq [E, H, I] e4m3, ws [E, H] f32. The HIP path
+    needs H%128==0 and I%128==0 and raises otherwise."""
+    contrib = torch.empty(aq.shape[0], wq.shape[1], dtype=torch.bfloat16,
+                          device=aq.device)
+    hip = _backend(aq)
+    if hip is None:
+        torch_ref.moe_down_scale_fp8(contrib, aq, as_, wq, ws, offs, counts,
+                                     order, flat_w)
+    else:
+        hip.moe_down_scale_fp8(contrib, aq, as_, wq, ws, offs, counts, order,
+                               flat_w)
+    return contrib
+
+
 build_cos_sin_cache = torch_ref.build_cos_sin_cache

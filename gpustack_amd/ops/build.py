@@ -18,7 +18,7 @@ CSRC = PKG_DIR / "csrc"
 SO_PATH = PKG_DIR / "_hip_ops.so"
 ARCH = os.environ.get("GPUSTACK_AMD_ARCH", "gfx950")
 
-HIP_SOURCES = ["pointwise.hip", "attn_decode.hip", "attn_prefill.hip", "skinny_gemm.hip", "gemm8.hip", "gemm8_lab.hip", "moe_gemm.hip", "w4_gemm.hip", "fp8_gemm.hip", "mla_decode.hip", "sample.hip", "lora.hip", "moe_route.hip"]
+HIP_SOURCES = ["pointwise.hip", "attn_decode.hip", "attn_prefill.hip", "skinny_gemm.hip", "gemm8.hip", "gemm8_lab.hip", "moe_gemm.hip", "moe_gemm_fp8.hip", "w4_gemm.hip", "fp8_gemm.hip", "mla_decode.hip", "sample.hip", "lora.hip", "moe_route.hip"]
 CPP_SOURCES = ["bindings.cpp"]
 # Per-source flags. lora.hip is built with the packed-f32 VALU ops
 # (v_pk_add/mul/fma_f32) turned off: the kernels' f32 reductions and the f32
@@ -26,8 +26,10 @@ CPP_SOURCES = ["bindings.cpp"]
 # with on the MI355X. It is not a speed choice: neither build uses scratch,
 # and the occupancies of docs/KERNELS.md are the same either way.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-# moe_route.hip is built the same way, for the same reason.
-EXTRA_FLAGS = {"lora.hip": _NO_PK_F32, "moe_route.hip": _NO_PK_F32}
+# moe_route.hip and moe_gemm_fp8.hip are built the same way, for the same
+# reason.
+EXTRA_FLAGS = {"lora.hip": _NO_PK_F32, "moe_route.hip": _NO_PK_F32,
+               "moe_gemm_fp8.hip": _NO_PK_F32}
 
 
 def _torch_paths():

@@ -32,6 +32,8 @@ void fp8_dequant_launch(void*, const void*, long, hipStream_t);
 void fp8_scale_out_launch(void*, const void*, const void*, long, int, int*, hipStream_t);
 void fp8_mfma_probe_launch(float*, const void*, const void*, hipStream_t);
 void lora_apply_launch(void*, const void*, const void*, const void*, float*, const int*, const int*, int, int, int, int, int, int, int, int, int, int, int, int*, hipStream_t);
+void moe_gate_up_silu_fp8_launch(void*, const void*, const float*, const void*, const float*, const int*, const int*, const int*, int, int, int, int*, hipStream_t);
+void moe_down_scale_fp8_launch(void*, const void*, const float*, const void*, const float*, const int*, const int*, const int*, const float*, int, int, int, int*, hipStream_t);
 void moe_route_launch(int*, float*, const float*, const float*, int, int, int, int, int, int, int, float, int*, hipStream_t);
 void moe_align_launch(int*, int*, int*, int*, const int*, int, int, int, hipStream_t);
 
@@ -555,6 +557,65 @@ at::Tensor fp8_mfma_probe(at::Tensor a, at::Tensor b) {
   return d;
 }
 
+// FP8 expert banks (moe_gemm_fp8.hip): wq [E, 2I, H] / [E, H, I] e4m3 with
+// one f32 scale per expert output row, activations quantized per row.
+void moe_gate_up_silu_fp8(at::Tensor act, at::Tensor xq, at::Tensor xs,
+                          at::Tensor wq, at::Tensor ws, at::Tensor s_tok,
+                          at::Tensor offs, at::Tensor counts) {
+  check_bf16(act, "act"); check_fp8(xq, "xq"); check_fp8(wq, "wq");
+  check_f32(xs, "xs"); check_f32(ws, "ws");
+  for (auto* t : {&s_tok, &offs, &counts}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt &&
+                t->is_contiguous());
+  }
+  TORCH_CHECK(act.dim() == 2 && xq.dim() == 2 && wq.dim() == 3);
+  const int E = wq.size(0), H = xq.size(1);
+  const int I = (int)(wq.size(1) / 2);
+  TORCH_CHECK(wq.size(1) == 2L * I && wq.size(2) == H && act.size(1) == I);
+  TORCH_CHECK(xs.numel() == xq.size(0) && ws.numel() == (long)E * 2 * I);
+  TORCH_CHECK(act.size(0) == s_tok.size(0));
+  TORCH_CHECK(offs.numel() == E && counts.numel() == E);
+  int err = 0;
+  moe_gate_up_silu_fp8_launch(act.data_ptr(), xq.data_ptr(),
+                              xs.data_ptr<float>(), wq.data_ptr(),
+                              ws.data_ptr<float>(), s_tok.data_ptr<int>(),
+                              offs.data_ptr<int>(), counts.data_ptr<int>(), E,
+                              H, I, &err, cur_stream(xq));
+  TORCH_CHECK(!err, "moe_gate_up_silu_fp8: unsupported dims H=", H, " I=", I,
+              " (need H%128==0, I%128==0)");
+  HIP_CHECK_LAST();
+}
+
+void moe_down_scale_fp8(at::Tensor contrib, at::Tensor aq, at::Tensor as,
+                        at::Tensor wq, at::Tensor ws, at::Tensor offs,
+                        at::Tensor counts, at::Tensor order,
+                        at::Tensor flat_w) {
+  check_bf16(contrib, "contrib"); check_fp8(aq, "aq"); check_fp8(wq, "wq");
+  check_f32(as, "as"); check_f32(ws, "ws"); check_f32(flat_w, "flat_w");
+  for (auto* t : {&offs, &counts, &order}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt &&
+                t->is_contiguous());
+  }
+  TORCH_CHECK(contrib.dim() == 2 && aq.dim() == 2 && wq.dim() == 3);
+  const int E = wq.size(0), H = wq.size(1), I = wq.size(2);
+  TORCH_CHECK(aq.size(1) == I && contrib.size(1) == H);
+  const long TK = aq.size(0);
+  TORCH_CHECK(contrib.size(0) == TK && order.numel() == TK &&
+              flat_w.numel() == TK && as.numel() == TK);
+  TORCH_CHECK(ws.numel() == (long)E * H);
+  TORCH_CHECK(offs.numel() == E && counts.numel() == E);
+  int err = 0;
+  moe_down_scale_fp8_launch(contrib.data_ptr(), aq.data_ptr(),
+                            as.data_ptr<float>(), wq.data_ptr(),
+                            ws.data_ptr<float>(), offs.data_ptr<int>(),
+                            counts.data_ptr<int>(), order.data_ptr<int>(),
+                            flat_w.data_ptr<float>(), E, H, I, &err,
+                            cur_stream(aq));
+  TORCH_CHECK(!err, "moe_down_scale_fp8: unsupported dims H=", H, " I=", I,
+              " (need H%128==0, I%128==0)");
+  HIP_CHECK_LAST();
+}
+
 // out[row_idx] += lora delta of the tile's slot (lora.hip). seg_starts: first
 // output column of each of the site's P projections.
 void lora_apply(at::Tensor out, at::Tensor x, at::Tensor a_site,
@@ -717,6 +778,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("counts"), py::arg("order"), py::arg("flat_w"),
         py::arg("bias") = py::none(),
         "grouped MoE down GEMM + routing-weight scale/scatter");
+  m.def("moe_gate_up_silu_fp8", &moe_gate_up_silu_fp8,
+        py::arg("act"), py::arg("xq"), py::arg("xs"), py::arg("wq"),
+        py::arg("ws"), py::arg("s_tok"), py::arg("offs"), py::arg("counts"),
+        "grouped MoE gate/up GEMM + SiLU on e4m3 codes (W8A8 expert banks)");
+  m.def("moe_down_scale_fp8", &moe_down_scale_fp8,
+        py::arg("contrib"), py::arg("aq"), py::arg("as_"), py::arg("wq"),
+        py::arg("ws"), py::arg("offs"), py::arg("counts"), py::arg("order"),
+        py::arg("flat_w"),
+        "grouped MoE down GEMM on e4m3 codes + routing-weight scale/scatter");
   m.def("moe_route", &moe_route,
         py::arg("logits"), py::arg("top_k"), py::arg("sigmoid"),
         py::arg("renorm"), py::arg("bias") = py::none(),

@@ -472,6 +472,37 @@ def fp8_linear(x: torch.Tensor, qw: torch.Tensor, ws: torch.Tensor,
     return out
 
 
+def moe_gate_up_silu_fp8(act: torch.Tensor, xq: torch.Tensor,
+                         xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor,
+                         s_tok: torch.Tensor, offs: torch.Tensor,
+                         counts: torch.Tensor) -> None:
+    """FP8 expert banks, gate/up (contract: ops.moe_gate_up_silu_fp8), one
+    sorted assignment at a time: fp8_gemm's scale order on each half, silu
+    and the product in f32, one rounding to act.dtype."""
+    I = act.shape[1]
+    for e, (o, c) in enumerate(zip(offs.tolist(), counts.tolist())):
+        w = wq[e].float()
+        for j in range(o, o + c):
+            t = int(s_tok[j])
+            gu = (w @ xq[t].float()) * xs[t].float() * ws[e].float()
+            g, u = gu[:I], gu[I:]
+            act[j] = g / (1.0 + torch.exp(-g)) * u
+
+
+def moe_down_scale_fp8(contrib: torch.Tensor, aq: torch.Tensor,
+                       as_: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor,
+                       offs: torch.Tensor, counts: torch.Tensor,
+                       order: torch.Tensor, flat_w: torch.Tensor) -> None:
+    """FP8 expert banks, down (contract: ops.moe_down_scale_fp8): row scale,
+    column scale, then the routing weight, one rounding to contrib.dtype."""
+    for e, (o, c) in enumerate(zip(offs.tolist(), counts.tolist())):
+        w = wq[e].float()
+        for j in range(o, o + c):
+            oj = int(order[j])
+            contrib[oj] = ((w @ aq[j].float()) * as_[j].float()
+                           * ws[e].float() * flat_w[oj].float())
+
+
 def lora_apply(out: torch.Tensor, x: torch.Tensor, A_site: torch.Tensor,
                B_site: torch.Tensor, seg_starts, row_idx: torch.Tensor,
                tiles: torch.Tensor) -> None:

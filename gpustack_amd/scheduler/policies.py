@@ -87,7 +87,12 @@ def _weight_bytes(model: dict, spec: ModelSpec, tp: int) -> int:
     at full size, everything else is halved, plus 4 B per output row of the
     packed projections for the f32 scales. MoE specs get no reduction
     (expert banks stay bf16; the claim must never fall below what stays
-    resident)."""
+    resident).
+
+    quantize_runtime=fp8_moe on a MoE spec without MLA whose expert banks
+    are eligible for packing at this tp: the expert-bank bytes are halved,
+    plus 4 B per expert output row; everything else is counted at bf16
+    size (the attention reduction is not claimed on top)."""
     bp = model.get("backend_parameters") or {}
     w = spec.weight_bytes() // tp
     if bp.get("quantize_runtime") == "w4":
@@ -95,7 +100,31 @@ def _weight_bytes(model: dict, spec: ModelSpec, tp: int) -> int:
     elif (bp.get("quantize_runtime") == "fp8" and spec.num_experts == 0
           and not spec.kv_lora_rank):
         w = fp8_weight_bytes(spec) // tp
+    elif (bp.get("quantize_runtime") == "fp8_moe" and spec.num_experts > 0
+          and not spec.kv_lora_rank and spec.moe_act == "silu"
+          and not spec.moe_bias and spec.hidden_size % 128 == 0
+          and spec.moe_intermediate_size % (128 * tp) == 0):
+        w = fp8_moe_weight_bytes(spec) // tp
     return w
+
+
+def expert_bank_bytes(spec: ModelSpec) -> int:
+    """bf16 bytes of the routed expert banks of a MoE spec (all shards)."""
+    moe_layers = spec.num_layers - min(spec.first_k_dense_replace,
+                                       spec.num_layers)
+    return (spec.num_experts * 3 * spec.hidden_size
+            * spec.moe_intermediate_size * 2 * moe_layers)
+
+
+def fp8_moe_weight_bytes(spec: ModelSpec) -> int:
+    """Resident bytes of a MoE spec under quantize_runtime=fp8_moe (all
+    shards together): e4m3 banks and (2I + H) * E f32 scales per MoE layer;
+    the rest at bf16 size."""
+    moe_layers = spec.num_layers - min(spec.first_k_dense_replace,
+                                       spec.num_layers)
+    rows = ((2 * spec.moe_intermediate_size + spec.hidden_size)
+            * spec.num_experts * moe_layers)
+    return spec.weight_bytes() - expert_bank_bytes(spec) // 2 + 4 * rows
 
 
 def fp8_weight_bytes(spec: ModelSpec) -> int:
