@@ -40,6 +40,11 @@ class DecodeGraphRunner:
         # one row per sequence: the captured step may fold rope and the
         # cache write into the attention kernel (read at capture time)
         self.fused_decode = rps == 1 and ops.fused_decode_enabled()
+        # rows of a captured step come in windows of rps per sequence; with
+        # the verify kernel on (read at capture time) the window size is
+        # baked into the graphs
+        self.rows_per_seq = rps
+        self.verify_windows = rps > 1 and ops.verify_kernel_enabled()
         self.max_bs = min(cfg.max_num_seqs * rps, BUCKETS[-1])
         self.buckets = [b for b in BUCKETS if b <= self.max_bs]
         if self.buckets[-1] != self.max_bs:
@@ -91,6 +96,7 @@ class DecodeGraphRunner:
             block_tables=self.block_tables[:bs],
             seq_lens=self.seq_lens[:bs],
             fused_decode=self.fused_decode,
+            rows_per_seq=self.rows_per_seq,
         )
 
     def capture(self) -> None:
@@ -126,6 +132,8 @@ class DecodeGraphRunner:
         return ((not batch.is_prefill)
                 and not batch.is_suffix
                 and len(batch.seqs) * batch.rows_per_seq <= self.max_bs
+                and (batch.rows_per_seq == self.rows_per_seq
+                     or not self.verify_windows)
                 and bool(self.graphs))
 
     def run(self, batch: ScheduledBatch, token_src: torch.Tensor | None = None) -> torch.Tensor:

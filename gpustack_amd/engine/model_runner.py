@@ -750,6 +750,7 @@ class ModelRunner:
                 fused_decode=(rps == 1
                               and getattr(self.cfg, "speculative", None) is None
                               and ops.fused_decode_enabled()),
+                rows_per_seq=rps,
             )
         slots = self._row_lora_slots(batch)
         if slots is not None:

@@ -60,6 +60,10 @@ class ForwardMeta:
     # attention layers may fold rope and the cache write into the decode
     # kernel (ops.paged_attn_decode_fused)
     fused_decode: bool = False
+    # speculative-verify decode step: rows i*rows_per_seq .. +rows_per_seq-1
+    # are the window of one sequence and share its block table, so attention
+    # layers may take ops.paged_attn_verify (one KV pass per window)
+    rows_per_seq: int = 1
 
 
 class W4Pack:
@@ -262,6 +266,13 @@ class Attention(nn.Module):
             ops.paged_prefill_attn(out, q, k_cache, v_cache,
                                    meta.block_tables, starts, hists, news,
                                    self.scale, tiles=tiles, **sw)
+        elif (meta.rows_per_seq > 1 and ops.verify_kernel_enabled()
+              and ops.verify_kernel_supported(
+                  self.hq, self.hkv, self.d, meta.rows_per_seq,
+                  k_cache.dtype, ext=bool(sw))):
+            ops.paged_attn_verify(
+                out, q, k_cache, v_cache, meta.block_tables, meta.seq_lens,
+                meta.rows_per_seq, self.scale)
         else:
             ops.paged_attn_decode(
                 out, q, k_cache, v_cache, meta.block_tables, meta.seq_lens,

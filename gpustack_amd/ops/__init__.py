@@ -217,6 +217,39 @@ def paged_attn_decode_fused(out, q, k, v, k_cache, v_cache, positions,
                                     seq_lens, scale)
 
 
+def verify_kernel_enabled() -> bool:
+    """GPUSTACK_AMD_VERIFY_KERNEL=1 sends the speculative-verify step to
+    paged_attn_verify; default off (the rows run as flattened decode rows)."""
+    return os.environ.get("GPUSTACK_AMD_VERIFY_KERNEL", "0") == "1"
+
+
+def verify_kernel_supported(hq: int, hkv: int, d: int, rows_per_seq: int,
+                            kv_dtype, ext: bool = False) -> bool:
+    """Shapes paged_attn_verify takes: head_dim 128, bf16 KV pool, windows of
+    2..8 rows with rows_per_seq * GQ <= 64, and none of the sink / window /
+    softcap variants (`ext`)."""
+    return (not ext and d == 128 and kv_dtype == torch.bfloat16
+            and hkv > 0 and hq % hkv == 0
+            and 2 <= rows_per_seq <= 8 and rows_per_seq * (hq // hkv) <= 64)
+
+
+def paged_attn_verify(out, q, k_cache, v_cache, block_tables, seq_lens,
+                      rows_per_seq: int, scale: float) -> None:
+    """Attention of a speculative-verify step: rows g*W .. g*W+W-1
+    (W = rows_per_seq) are the window of one sequence. They share the block
+    table of the group's first row, which must cover the group's largest
+    seq_len; row r attends to keys t < seq_lens[r] (<= 0 writes zeros). N need
+    not be a multiple of W. One MFMA pass over the pages per (window, kv
+    head). The HIP path raises outside verify_kernel_supported."""
+    hip = _backend(q)
+    if hip is not None:
+        hip.paged_attn_verify(out, q, k_cache, v_cache, block_tables,
+                              seq_lens, rows_per_seq, scale)
+    else:
+        torch_ref.paged_attn_verify(out, q, k_cache, v_cache, block_tables,
+                                    seq_lens, rows_per_seq, scale)
+
+
 def mla_decode(ctx_out, q_cat, lat_cache, block_tables, seq_lens,
                scale: float) -> None:
     """MLA absorbed decode (DeepSeek): ctx_out[N,H,512] f32 = softmax

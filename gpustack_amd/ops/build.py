@@ -18,7 +18,7 @@ CSRC = PKG_DIR / "csrc"
 SO_PATH = PKG_DIR / "_hip_ops.so"
 ARCH = os.environ.get("GPUSTACK_AMD_ARCH", "gfx950")
 
-HIP_SOURCES = ["pointwise.hip", "attn_decode.hip", "attn_prefill.hip", "skinny_gemm.hip", "gemm8.hip", "gemm8_lab.hip", "moe_gemm.hip", "moe_gemm_fp8.hip", "w4_gemm.hip", "fp8_gemm.hip", "mla_decode.hip", "sample.hip", "lora.hip", "moe_route.hip"]
+HIP_SOURCES = ["pointwise.hip", "attn_decode.hip", "attn_verify.hip", "attn_prefill.hip", "skinny_gemm.hip", "gemm8.hip", "gemm8_lab.hip", "moe_gemm.hip", "moe_gemm_fp8.hip", "w4_gemm.hip", "fp8_gemm.hip", "mla_decode.hip", "sample.hip", "lora.hip", "moe_route.hip"]
 CPP_SOURCES = ["bindings.cpp"]
 # Per-source flags. lora.hip is built with the packed-f32 VALU ops
 # (v_pk_add/mul/fma_f32) turned off: the kernels' f32 reductions and the f32

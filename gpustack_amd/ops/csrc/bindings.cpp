@@ -15,6 +15,7 @@ void sample_launch(long*, const void*, const float*, const int*, const float*, c
 void mla_decode_launch(float*, const void*, const void*, const int*, const int*, int, int, int, int, int, int, float, int*, hipStream_t);
 void paged_attn_decode_launch(void*, const void*, const void*, const void*, const int*, const int*, int, int, int, int, int, float, long, int, const float*, int, float, int*, hipStream_t);
 void paged_attn_decode_fused_launch(void*, const void*, const void*, const void*, void*, void*, const long*, const float*, const long*, const int*, const int*, int, int, int, int, int, float, long, long, long, int*, hipStream_t);
+void paged_attn_verify_launch(void*, const void*, const void*, const void*, const int*, const int*, int, int, int, int, int, float, long, int*, hipStream_t);
 void flash_prefill_launch(void*, const void*, const void*, const void*, const int*, const int*, const int*, int, int, int, int, int, float, long, long, long, const float*, int, float, int*, hipStream_t);
 void flash_prefill_paged_launch(void*, const void*, const void*, const void*, const int*, const int*, const int*, const int*, const int*, const int*, int, int, int, int, int, float, long, const float*, int, float, int*, hipStream_t);
 void mfma_probe_launch(float*, const void*, const void*, hipStream_t);
@@ -295,6 +296,54 @@ void paged_attn_decode_fused(at::Tensor out, at::Tensor q, at::Tensor k,
       cur_stream(q));
   TORCH_CHECK(!err, "paged_attn_decode_fused: unsupported head_dim/GQ "
               "combination: D=", D, " Hq=", Hq, " Hkv=", Hkv);
+  HIP_CHECK_LAST();
+}
+
+// Speculative-verify attention: rows g*W .. g*W+W-1 are the window of one
+// sequence and attend to the same pages, read once per (window, kv head) on
+// the matrix cores. Allocates nothing, never syncs.
+// Contract (the engine's verify step; not checkable without a sync): the
+// block-table row of a group's first row serves the whole group and covers
+// its largest seq_len. Row r attends to keys t < seq_lens[r].
+void paged_attn_verify(at::Tensor out, at::Tensor q, at::Tensor k_cache,
+                       at::Tensor v_cache, at::Tensor block_tables,
+                       at::Tensor seq_lens, long rows_per_seq, double scale) {
+  check_bf16(out, "out");
+  const long qstride = row_stride_3d(q, "q");
+  check_cache(k_cache, "k_cache"); check_cache(v_cache, "v_cache");
+  TORCH_CHECK(!is_fp8_cache(k_cache) && !is_fp8_cache(v_cache),
+              "paged_attn_verify: bf16 KV pools only (fp8 pools keep the "
+              "flattened decode kernel)");
+  const int N = q.size(0), Hq = q.size(1), D = q.size(2);
+  TORCH_CHECK(D == 128, "paged_attn_verify: head_dim must be 128, got ", D);
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 16
+                  && k_cache.size(3) == D && v_cache.sizes() == k_cache.sizes(),
+              "paged_attn_verify assumes [blocks, Hkv, 16, 128] pools");
+  const int Hkv = k_cache.size(1);
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "Hq must be a multiple of Hkv");
+  const long W = rows_per_seq;
+  TORCH_CHECK(W >= 2 && W <= 8, "paged_attn_verify: rows_per_seq must be in "
+              "2..8, got ", W);
+  TORCH_CHECK(W * (Hq / Hkv) <= 64, "paged_attn_verify: rows_per_seq * GQ must "
+              "be <= 64, got ", W, " * ", Hq / Hkv);
+  TORCH_CHECK(out.dim() == 3 && out.size(0) == N && out.size(1) == Hq
+                  && out.size(2) == D, "out must be [N, Hq, 128]");
+  check_row_param(seq_lens, at::kInt, N, "seq_lens");
+  TORCH_CHECK(block_tables.is_cuda() && block_tables.scalar_type() == at::kInt
+                  && block_tables.is_contiguous() && block_tables.dim() == 2
+                  && block_tables.size(0) == N,
+              "block_tables must be contiguous int32 [N, max_blocks]");
+  // 16 B vector loads of the q rows
+  TORCH_CHECK(qstride % 8 == 0 && q.storage_offset() % 8 == 0,
+              "q rows must be 16-byte aligned");
+  int err = 0;
+  paged_attn_verify_launch(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(),
+                           v_cache.data_ptr(), block_tables.data_ptr<int>(),
+                           seq_lens.data_ptr<int>(), N, Hq, Hkv, (int)W,
+                           (int)block_tables.size(1), (float)scale, qstride,
+                           &err, cur_stream(q));
+  TORCH_CHECK(!err, "paged_attn_verify: unsupported shape: Hq=", Hq, " Hkv=",
+              Hkv, " rows_per_seq=", W);
   HIP_CHECK_LAST();
 }
 
@@ -752,6 +801,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"),
         py::arg("cos_sin"), py::arg("slot_mapping"), py::arg("block_tables"),
         py::arg("seq_lens"), py::arg("scale"));
+  m.def("paged_attn_verify", &paged_attn_verify,
+        "speculative-verify paged GQA attention, one KV pass per draft window",
+        py::arg("out"), py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("block_tables"), py::arg("seq_lens"), py::arg("rows_per_seq"),
+        py::arg("scale"));
   m.def("flash_prefill", &flash_prefill, "varlen causal MFMA prefill attention",
         py::arg("out"), py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("tile_start"), py::arg("tile_q0"), py::arg("tile_len"),

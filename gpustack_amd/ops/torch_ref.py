@@ -343,6 +343,17 @@ def paged_attn_decode(
         out[i] = (att @ vals).squeeze(1).to(out.dtype)
 
 
+def paged_attn_verify(out, q, k_cache, v_cache, block_tables, seq_lens,
+                      rows_per_seq: int, scale: float) -> None:
+    """Speculative-verify attention: rows g*W .. g*W+W-1 (W = rows_per_seq)
+    are one sequence's window and all take the block table of the group's
+    first row; row r attends to keys t < seq_lens[r]."""
+    first = torch.arange(q.shape[0], device=block_tables.device)
+    first = first // rows_per_seq * rows_per_seq
+    paged_attn_decode(out, q, k_cache, v_cache, block_tables[first], seq_lens,
+                      scale)
+
+
 def varlen_prefill_attn(
     out: torch.Tensor,
     q: torch.Tensor,
